@@ -17,7 +17,12 @@ one all-reduce that assembles every sequence's poses on every rank, after which 
 sequence alone on its own GPU (one vo_reset + call per sequence, as the reference's one run() per
 sequence) and checks the gathered rows bit for bit.
 
-Also on the JSON line:
+A plain run (bench.py --gpus 1 --steps N --warmup W) renders the sequences, warms up, times the N
+steps and prints the line; --dump-outputs DIR also writes what the last timed step returned (poses
+(frames, 3, 4), status, info, the rank's sequences in stream order) as float64 DIR/<name>.npy.  The
+frames are seeded, so two builds run with the same arguments can be compared array for array.
+
+With --full, also on the JSON line (None in a plain run):
   roofline      the kernel with the largest per-frame time (the stencil: the extract queue it runs
                 on is the critical path, busy ~89 % of a step; the pose queue overlaps it):
                 SURVEY 8(d)'s algorithmic bytes per launch / its average launch time (HIP events on
@@ -579,6 +584,11 @@ def shard_main(args, world: int, rank: int, local: int):
     dt, _ = aggregate(dist, dt, 0, world, backend=args.backend, local=dev)
     value = F * args.steps / dt
     rows = np.concatenate([res.poses.reshape(-1, 12), res.status.reshape(-1, 1).astype(np.float64)], axis=1)
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        tag = "" if world == 1 else f"_rank{rank}"
+        np.save(os.path.join(args.dump_outputs, f"poses{tag}.npy"), res.poses.reshape(-1, 3, 4).astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, f"status{tag}.npy"), res.status.reshape(-1).astype(np.float64))
     if dist is not None:
         allrows = [None] * world
         dist.all_gather_object(allrows, (rows, res.runs, res.a - res.start))
@@ -638,7 +648,13 @@ def main():
     ap.add_argument("--device", type=int, default=-1, help="GPU of every rank (default: LOCAL_RANK; one-GPU rehearsal: 0)")
     ap.add_argument("--shard-sequence", action="store_true",
                     help="one sequence (sequences x frames frames) split over the ranks (within-sequence sharding)")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr")
+    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr (with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the CPU baseline and its oracle rows, "
+                         "the per-kernel breakdown and roofline, the separate-run check, the variants, config 5 at "
+                         "N > 1 (--no-cpu / --no-variants / --no-check drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (poses, status, info) as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -653,7 +669,9 @@ def main():
     my_seqs = rank_sequences(S, rank, world, args.scaling)
     owners = [rank_sequences(S, r, world, args.scaling) for r in range(world)]
     n_total = sum(len(o) for o in owners)
-    lead = rank == 0 and world == 1                      # the N = 1 variants
+    # a plain run renders its sequences, warms up, times the steps and prints the line; everything
+    # else on the line (None in a plain run) is measured and checked under --full
+    lead = args.full and rank == 0 and world == 1        # the N = 1 variants
     # the CPU baseline and its oracle-row check run on rank 0 at every world size (north_star: the
     # reference CPU path timed on the same box in the same run)
 
@@ -662,7 +680,7 @@ def main():
     workers = render_workers(world)
     # N > 1 with weak scaling: config 5 literally as well (8 sequences in all, sequence s on GPU s mod G),
     # timed after the weak-scaling line's run and reported beside it (config5_strong)
-    c5_seqs = rank_sequences(8, rank, world, "strong") if world > 1 and args.scaling == "weak" else []
+    c5_seqs = rank_sequences(8, rank, world, "strong") if args.full and world > 1 and args.scaling == "weak" else []
     specs = [(W, H, F, s, args.motion) for s in my_seqs] + [(W, H, F, s, args.motion) for s in c5_seqs
                                                             if s not in my_seqs]
     extra_specs = {}
@@ -677,7 +695,7 @@ def main():
     extra = {tag: (rendered[n_mine + i], SceneSequence(sp[0], sp[1], nframes=sp[2], seq=sp[3], step=sp[4]))
              for i, (tag, sp) in enumerate(extra_specs.items())}
     cpu, oracle_rows = None, None
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         s0, fr0 = seqs[my_seqs[0]]
         cpu, oracle_rows = cpu_baseline(fr0, s0, args.cpu_seconds, args.max_kpts, cpu_share())
 
@@ -728,35 +746,44 @@ def main():
     for _ in range(max(args.warmup, 1)):
         step()
     warm = {s: (last[s][0].copy(), last[s][1].copy()) for s in my_seqs}
-    # per-kernel breakdown (untimed): every launch bracketed by events
-    bd = []
-    step(timing=1, stats=bd)
-    ks = {k: (float(np.mean([b[k][0] for b in bd if k in b])), float(np.mean([b[k][1] for b in bd if k in b])))
-          for k in KERNELS + ["ransac_pose"] if any(k in b for b in bd)}
-    info_all = np.concatenate([last[s][2] for s in my_seqs])
-    per_frame = {k: ks[k][0] / ks[k][1] if k in ks and ks[k][1] > 0 else 0.0 for k in KERNELS + ["ransac_pose"]}
-    dominant = dominant_kernel(per_frame)
-    kidx = KERNELS.index(dominant)
+    live_timing, live = 0, None
+    if args.full:
+        # per-kernel breakdown (untimed): every launch bracketed by events
+        bd = []
+        step(timing=1, stats=bd)
+        ks = {k: (float(np.mean([b[k][0] for b in bd if k in b])), float(np.mean([b[k][1] for b in bd if k in b])))
+              for k in KERNELS + ["ransac_pose"] if any(k in b for b in bd)}
+        per_frame = {k: ks[k][0] / ks[k][1] if k in ks and ks[k][1] > 0 else 0.0 for k in KERNELS + ["ransac_pose"]}
+        dominant = dominant_kernel(per_frame)
+        # the roofline's live figure: two events around every 4th dominant launch of the timed steps
+        live_timing, live = 100 + KERNELS.index(dominant), []
 
     barrier()
-    live = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(timing=100 + kidx, stats=live)          # two events around every 4th dominant launch
+        step(timing=live_timing, stats=live)
     t1 = time.perf_counter()
     barrier()
     dt = t1 - t0
+    info_all = np.concatenate([last[s][2] for s in my_seqs])
+    if args.dump_outputs:
+        # what the last timed step returned to its caller, the rank's sequences in stream order
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        tag = "" if world == 1 else f"_rank{rank}"
+        for name, i in (("poses", 0), ("status", 1), ("info", 2)):
+            np.save(os.path.join(args.dump_outputs, f"{name}{tag}.npy"),
+                    np.concatenate([last[s][i] for s in my_seqs]).astype(np.float64))
     frames_rank = args.steps * F * len(my_seqs)
     dt, value = aggregate(dist, dt, frames_rank, world, backend=args.backend, local=dev)
     repeat_equal = all(np.array_equal(warm[s][0], last[s][0]) and np.array_equal(warm[s][1], last[s][1])
                        for s in my_seqs)
-    rows = {s: np.concatenate([last[s][0].reshape(F, 12), last[s][1].reshape(F, 1).astype(np.float64)], axis=1)
-            for s in my_seqs}
-    gathered = gather_poses(dist, rows, owners, F, backend=args.backend, local=dev)
     # every rank runs each of its sequences alone, as the reference would (one run() each); those
     # rows are gathered too and rank 0 checks every sequence's stream rows against them bit for bit
     gather_ok = None
-    if not args.no_check:
+    if args.full and not args.no_check:
+        rows = {s: np.concatenate([last[s][0].reshape(F, 12), last[s][1].reshape(F, 1).astype(np.float64)], axis=1)
+                for s in my_seqs}
+        gathered = gather_poses(dist, rows, owners, F, backend=args.backend, local=dev)
         sep = gather_poses(dist, {s: separate(s, seqs[s][1]) for s in my_seqs}, owners, F, backend=args.backend,
                            local=dev)
         gather_ok = bool(np.array_equal(sep.view(np.int64), gathered.view(np.int64)))
@@ -822,29 +849,32 @@ def main():
         variants = run_variants(args, ctx, W, H, seqs[s0][1], gts[s0], extra, Context)
 
     if rank == 0:
-        prof, psrc = load_profile(W, H, args.match_bits)
-        forms = ctx.kernel_forms()
-        roof = roofline_entry(dominant, live, info_all, W, H, prof, psrc, forms)
         path_bytes = algorithmic_bytes("path", W, H, info_all)
-        kern = {}
-        for k in KERNELS:
-            if k not in ks:
-                continue
-            r = profile_row(prof, k, forms)
-            kern[k] = {"symbols": forms[k],"us_per_frame": round(per_frame[k] * 1e3, 4), "us_per_launch": round(ks[k][0] * 1e3, 2),
-                       "frames_per_launch": round(ks[k][1], 2),
-                       "algorithmic_bytes_per_frame": round(algorithmic_bytes(k, W, H, info_all), 1),
-                       "queue": "pose" if k in POSE_QUEUE else ("trajectory" if k == "trajectory" else "extract"),
-                       "pmc_hbm_bytes_per_launch": r["hbm_bytes"] if r else None,
-                       "valu_issue_frac": r["valu_issue_frac"] if r else None}
-        if "ransac_pose" in ks and ks["ransac_pose"][1] > 0:
-            kern["ransac_pose"] = {"us_per_frame": round(per_frame["ransac_pose"] * 1e3, 4), "queue": "pose",
-                                   "note": "the first RANSAC chunk of each pass (the pose queue's share of 'ransac')"}
+        roof, kern = None, None
+        if args.full:
+            prof, psrc = load_profile(W, H, args.match_bits)
+            forms = ctx.kernel_forms()
+            roof = roofline_entry(dominant, live, info_all, W, H, prof, psrc, forms)
+            kern = {}
+            for k in KERNELS:
+                if k not in ks:
+                    continue
+                r = profile_row(prof, k, forms)
+                kern[k] = {"symbols": forms[k],"us_per_frame": round(per_frame[k] * 1e3, 4), "us_per_launch": round(ks[k][0] * 1e3, 2),
+                           "frames_per_launch": round(ks[k][1], 2),
+                           "algorithmic_bytes_per_frame": round(algorithmic_bytes(k, W, H, info_all), 1),
+                           "queue": "pose" if k in POSE_QUEUE else ("trajectory" if k == "trajectory" else "extract"),
+                           "pmc_hbm_bytes_per_launch": r["hbm_bytes"] if r else None,
+                           "valu_issue_frac": r["valu_issue_frac"] if r else None}
+            if "ransac_pose" in ks and ks["ransac_pose"][1] > 0:
+                kern["ransac_pose"] = {"us_per_frame": round(per_frame["ransac_pose"] * 1e3, 4), "queue": "pose",
+                                       "note": "the first RANSAC chunk of each pass (the pose queue's share of 'ransac')"}
         st_all = np.concatenate([last[s][1] for s in my_seqs])
         line = {
             "metric": METRIC, "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
             "scaling": args.scaling, "vs_baseline": None, "dtype": "u8/f32/u32/f64", "data": "synthetic",
+            "full": args.full,
             "config": {"workload": ("kitti_1241x376_2000kpts_full_path" if (W, H) == (1241, 376)
                                     else f"{W}x{H}_{args.max_kpts}kpts_full_path"),
                        "sequences": n_total, "frames_per_sequence": F, "sequences_per_gpu": len(my_seqs),
@@ -883,7 +913,7 @@ def main():
         }
         if c5 is not None:
             line["config5_strong"] = c5
-        if args.breakdown:
+        if args.full and args.breakdown:
             for k in KERNELS:
                 if k in ks:
                     print(f"{k:14s} {per_frame[k] * 1e3:9.2f} us/frame  {ks[k][0] * 1e3:9.1f} us/launch  "

@@ -175,7 +175,7 @@ def test_bench_line_world2_gloo_is_complete():
     q = ctx.Queue()
     port = _free_port()
     argv = ["--gpus", "2", "--backend", "gloo", "--device", "0", "--frames", "3", "--sequences", "1",
-            "--steps", "1", "--warmup", "1", "--cpu-seconds", "0.2", "--no-variants"]
+            "--steps", "1", "--warmup", "1", "--cpu-seconds", "0.2", "--no-variants", "--full"]
     procs = [ctx.Process(target=_bench_rank, args=(r, 2, port, q, argv)) for r in range(2)]
     for p in procs:
         p.start()
@@ -197,3 +197,54 @@ def test_bench_line_world2_gloo_is_complete():
         assert roof["bound"] == "hbm" and roof["unit"] == "GB/s" and roof["achieved"] > 0
         assert roof["frac"] == pytest.approx(roof["achieved"] / roof["peak"])
     assert line["config5_strong"]["sequences_per_gpu"] == [4, 4]
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path, monkeypatch, capsys):
+    """A plain bench.main() (no --full) on the stand-in engine: --steps timed steps and no other run of
+    the engine, the headline fields on the line, everything --full adds left None, and --dump-outputs
+    writing the last timed step's arrays -- the oracle's own rows here -- identically from run to run."""
+    import json
+    import sys
+
+    import bench
+    from acs_visual_odometry_amd.synth import SceneSequence
+    calls = []
+
+    class Counting(_StandInContext):
+        def process_frames_device(self, df, timing=0):
+            calls.append(timing)
+            return super().process_frames_device(df, timing)
+
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("VO_CPU_SHARE", "1")                # render in this process
+    monkeypatch.setattr(bench, "context_class", lambda: Counting)
+    lines = []
+    for d in ("a", "b"):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--frames", "3", "--sequences", "2", "--steps", "2",
+                                          "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        bench.main()
+        lines.append(json.loads(capsys.readouterr().out.strip().splitlines()[-1]))
+    assert calls == [0] * 6                                 # (1 warmup + 2 timed steps) x 2 runs, untimed launches
+    line = lines[0]
+    assert line["metric"] == bench.METRIC and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["full"] is False
+    assert line["ms_per_step"] > 0 and line["value"] == pytest.approx(6 / (line["ms_per_step"] * 1e-3))
+    for k in ("roofline", "kernels", "variants", "cpu_baseline", "h2d_inclusive"):
+        assert line[k] is None
+    assert line["determinism"]["gathered_rows_equal_separate_runs"] is None
+    assert line["determinism"]["oracle_rows_equal"] is None
+    assert line["determinism"]["timed_rows_equal_warmup_rows"] is True
+    out = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("poses", "status", "info")}
+    assert out["poses"].shape == (6, 3, 4) and out["status"].shape == (6,) and out["info"].shape == (6, 8)
+    for n, a in out.items():
+        assert a.dtype == np.float64
+        assert np.array_equal(a.view(np.int64), np.load(tmp_path / "b" / f"{n}.npy").view(np.int64))
+    import oracle as O
+    for s in range(2):
+        seq = SceneSequence(nframes=3, seq=s)
+        vo = O.VO(O.config(seq.W, seq.H, K=seq.K.reshape(9), max_kpts=2000), gt=seq.gt())
+        for f in range(3):
+            p, st, _ = vo.process(seq.frame(f))
+            assert np.array_equal(out["poses"][3 * s + f], p) and out["status"][3 * s + f] == st
+        vo.close()

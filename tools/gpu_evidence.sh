@@ -24,7 +24,7 @@ for w in "$@"; do
   head -16 profiles/${R}_${w}_kernels.md | tail -12
 done
 case " $* " in *" bench "*)
-  timeout -k 10 600 python -u bench.py --breakdown > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full --breakdown > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; tail -20 $O/bench.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench.json'));r=d['roofline'];print('VALUE',round(d['value']),'dominant',r['kernel'],'live',r['avg_launch_ms'],'rocprof',r['rocprof_avg_launch_us'],r['traffic_source']);print(d['determinism']);print(json.dumps(d['variants'],indent=0)[:2500]);print(json.dumps(d['cpu_baseline'])[:500])"
   cat $O/bench.err;;
 esac
