@@ -33,7 +33,47 @@
 #include <vector>
 
 #include "vo_internal.h"
+#include "../../include/vo_freak_tables.h"
 #include "../../include/vo_mi355x.h"
+
+// Smallest NMS borders vo_create accepts, from the describe's pattern (vo_freak_points).  The NMS mask
+// admits keypoints bcol <= x <= W - bcol, brow <= y <= H - brow, and the describe reads the blurred
+// frame around each of them twice:
+//  - unrotated (the orientation sums), at (x + px, y + py): inside the frame iff
+//    bcol >= max|px| + 1 and brow >= max|py| + 1 (34 and 31);
+//  - rotated (the 512 tests), at ((int)(x + px c + py s), (int)(y + px s + py c)) (quirk 4: the
+//    transform is [[c, s], [s, c]]): both offsets lie in [-r, r], r = |(px, py)|, for every angle, so
+//    the truncated coordinates reach from -ceil(r) to floor(r) in either direction, which needs
+//    floor(r) + 1 on both borders -- 35, from (17, +-30), r = 34.48.  The reference and the oracle
+//    read these without a clamp; the kernels clamp, so below 35 they would stay inside the frame and
+//    compute something else than the reference.
+// Integer arithmetic only: floor(sqrt(q)) is the largest b with b * b <= q.
+namespace {
+constexpr int isqrt_floor(int q)
+{
+    int b = 0;
+    while ((b + 1) * (b + 1) <= q) ++b;
+    return b;
+}
+constexpr int iabs(int v) { return v < 0 ? -v : v; }
+constexpr int kFreakPoints[VO_FREAK_NPOINTS][2] = {VO_FREAK_POINTS_LIST};   // vo_freak_points, constexpr
+constexpr int min_border(int axis)          // axis 0: columns (x), 1: rows (y)
+{
+    int b = 0;
+    for (int i = 0; i < VO_FREAK_NPOINTS; ++i) {
+        const int px = kFreakPoints[i][0], py = kFreakPoints[i][1];
+        const int plain = iabs(axis == 0 ? px : py) + 1;
+        const int rotated = isqrt_floor(px * px + py * py) + 1;
+        b = plain > b ? plain : b;
+        b = rotated > b ? rotated : b;
+    }
+    return b;
+}
+constexpr int VO_MIN_BORDER_COL = min_border(0), VO_MIN_BORDER_ROW = min_border(1);
+static_assert(VO_MIN_BORDER_COL <= 37 && VO_MIN_BORDER_ROW <= 35, "the reference's borders must stay valid");
+static_assert(sizeof(vo_freak_points) == sizeof(kFreakPoints) && sizeof(vo_freak_patch) == VO_FREAK_NTESTS * sizeof(short),
+              "the tables of vo_freak_tables.h");
+}  // namespace
 
 
 struct vo_ctx {
@@ -849,6 +889,14 @@ int vo_create(const vo_config* cfg, vo_ctx** out)
     if (k.max_kpts < 1 || k.max_kpts > 4096) return VO_ERR_ARG;
     if (k.nms_k != 3) return VO_ERR_ARG;                     // the VO path uses k = 3
     if (!(k.resp_thr >= 0.0f)) return VO_ERR_ARG;
+    // every read of the describe inside the frame, for every keypoint the NMS mask admits (above).  The
+    // dummy keypoint (bcol, brow) of the describe's lanes past n needs no rule of its own: such lanes
+    // exist only in a wave that holds a keypoint (base < n), a keypoint exists only where the mask is
+    // not empty (bcol <= W - bcol, brow <= H - brow), and then (bcol, brow) is itself an admitted
+    // position.  A frame too small for any keypoint extracts none, and every describe wave returns
+    // before it reads.
+    if (k.border_col < VO_MIN_BORDER_COL || k.border_row < VO_MIN_BORDER_ROW) return VO_ERR_ARG;
+    if (!(k.ratio >= 0.0f) || !(k.sampson_thr >= 0.0)) return VO_ERR_ARG;   // NaN or negative
     if (k.match_bits != 32 && k.match_bits != 512) return VO_ERR_ARG;
     if (!(k.ransac_p > 0.0 && k.ransac_p < 1.0) || k.ransac_chunk_threads < 1) return VO_ERR_ARG;
     if (k.frame_batch < 0 || k.frame_batch > VO_MAX_BATCH) return VO_ERR_ARG;

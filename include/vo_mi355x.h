@@ -68,13 +68,23 @@ typedef struct {
     int width, height;
     int max_kpts;             /* N = 2000      feature_extraction_parallel_GPU.cpp:235 */
     int nms_k;                /* 3             feature_extraction_parallel_GPU.cpp:235 */
-    float resp_thr;           /* 20000         corner_detection_parallel_GPU.h:25      */
+    float resp_thr;           /* 20000         corner_detection_parallel_GPU.h:25; >= 0, not NaN */
     int border_row;           /* 35            corner_detection_parallel_GPU.cpp:157   */
-    int border_col;           /* 37            corner_detection_parallel_GPU.cpp:157   */
-    float ratio;              /* 0.75          VisualOdometry.cpp:35                   */
+    int border_col;           /* 37            corner_detection_parallel_GPU.cpp:157
+                                 Keypoints lie in border_col <= x <= W - border_col, border_row <= y
+                                 <= H - border_row.  Both borders must be >= 35: the describe samples
+                                 the 43 FREAK points around every keypoint without a bounds check in
+                                 the reference, unrotated (|dx| <= 33, |dy| <= 30) and rotated by the
+                                 keypoint's angle (offsets -35 .. +34 in either direction, from the
+                                 point (17, 30) at radius 34.48).  vo_create derives the bound from
+                                 vo_freak_points and returns VO_ERR_ARG below it.  There is no upper
+                                 bound: a frame smaller than twice a border has no keypoints. */
+    float ratio;              /* 0.75          VisualOdometry.cpp:35; >= 0, not NaN (0 accepts no
+                                 match, since best < ratio * second is strict)                 */
     int match_bits;           /* 32 (reference quirk 1) or 512 (matching_serial.cpp)   */
-    double ransac_p;          /* 0.99          VisualOdometry.cpp:130                  */
-    double sampson_thr;       /* 1.0           VisualOdometry.cpp:130                  */
+    double ransac_p;          /* 0.99          VisualOdometry.cpp:130; in (0, 1)       */
+    double sampson_thr;       /* 1.0           VisualOdometry.cpp:130; >= 0, not NaN (+inf is
+                                 allowed, as in vo_ransac_run)                                 */
     int ransac_chunk_threads; /* T             ransac.cpp:152-157 (CLI num_threads)    */
     uint64_t seed;            /* RANSAC sampler seed (replaces std::random_device)     */
     double K[9];              /* PoseUpdate.hpp:36-39                                  */

@@ -1,6 +1,7 @@
 """The C-ABI library loads and exports every symbol include/vo_mi355x.h declares (no GPU
 calls), and it carries gfx950 code objects only."""
 import ctypes as C
+import math
 import os
 import re
 import subprocess
@@ -80,6 +81,79 @@ def test_create_without_gpu_fails_loudly():
     from acs_visual_odometry_amd import Context
     with pytest.raises(RuntimeError):
         Context(1241, 376)
+
+
+def _create_rc(**overrides):
+    """vo_create's return code for the default 320 x 192 config with `overrides` (a context that
+    does get created, on a machine with a GPU, is destroyed at once)."""
+    from acs_visual_odometry_amd import _lib
+    L = _lib.load()
+    cfg = _lib.default_config(320, 192, **overrides)
+    h = C.c_void_p()
+    rc = L.vo_create(C.byref(cfg), C.byref(h))
+    if rc == 0:
+        L.vo_destroy(h)
+    else:
+        assert not h.value
+    return rc
+
+
+def _describe_reach():
+    """(columns, rows) the describe's reads need around a keypoint, from vo_freak_tables.h: the
+    listed offsets for the orientation sums, and for the rotated samples (int)(x + px c + py s),
+    (int)(y + px s + py c), whose offsets span [-r, r], r = |(px, py)|, over the angles."""
+    src = open(os.path.join(ROOT, "include", "vo_freak_tables.h")).read()
+    body = re.search(r"#define VO_FREAK_POINTS_LIST(.*?)#define", src, flags=re.S).group(1)
+    pts = [(int(a), int(b)) for a, b in re.findall(r"\{(-?\d+),\s*(-?\d+)\}", body)]
+    assert len(pts) == 43
+    rot = max(math.isqrt(x * x + y * y) for x, y in pts) + 1
+    return max(max(abs(x) for x, _ in pts) + 1, rot), max(max(abs(y) for _, y in pts) + 1, rot)
+
+
+VO_ERR_ARG = -1
+
+
+def test_create_rejects_borders_inside_the_describe_reach():
+    """Borders below the describe's reach would let it sample outside the frame (the reference reads
+    there unchecked); the bound follows from the pattern: 35 columns and 35 rows."""
+    bcol, brow = _describe_reach()
+    assert (bcol, brow) == (35, 35)
+    for col, row in [(bcol - 1, 35), (37, brow - 1), (33, 30), (0, 0), (-1, 35), (37, -35), (5, 5),
+                     (-2**31, -2**31)]:
+        assert _create_rc(border_col=col, border_row=row) == VO_ERR_ARG, (col, row)
+    for col, row in [(bcol, brow), (37, 35), (90, 60), (60, 90), (1000, 1000)]:
+        assert _create_rc(border_col=col, border_row=row) != VO_ERR_ARG, (col, row)
+
+
+def test_rotated_reach_is_attained_on_the_oracle():
+    """The rotated samples do reach -35 and +34: the oracle's own sin / cos at the angle of (17, 30)
+    and the describe's f32 expression, so 34 would not be enough."""
+    import numpy as np
+    import oracle as O
+    L = O.lib()
+    f = np.float32
+    lo, hi = 0, 0
+    for a in np.linspace(-math.pi, math.pi, 7201):
+        c, s = f(L.voo_det_cos(float(f(a)))), f(L.voo_det_sin(float(f(a))))
+        for px, py in ((17, 30), (17, -30), (-17, 30), (-17, -30)):
+            x = int((f(100.0) + f(px) * c) + f(py) * s) - 100
+            lo, hi = min(lo, x), max(hi, x)
+    assert (lo, hi) == (-35, 34)
+
+
+@pytest.mark.parametrize("field,bad", [("ratio", float("nan")), ("ratio", -0.5), ("ratio", -1e-30),
+                                       ("sampson_thr", float("nan")), ("sampson_thr", -1.0),
+                                       ("sampson_thr", -1e-300), ("sampson_thr", float("-inf")),
+                                       ("resp_thr", float("nan")), ("resp_thr", -1.0)])
+def test_create_rejects_nan_and_negative_thresholds(field, bad):
+    assert _create_rc(**{field: bad}) == VO_ERR_ARG
+
+
+@pytest.mark.parametrize("field,good", [("ratio", 0.0), ("ratio", 1.5), ("ratio", float("inf")),
+                                        ("sampson_thr", 0.0), ("sampson_thr", 0.25), ("sampson_thr", float("inf")),
+                                        ("resp_thr", 0.0), ("resp_thr", 1e7)])
+def test_create_accepts_the_threshold_range(field, good):
+    assert _create_rc(**{field: good}) != VO_ERR_ARG
 
 
 def test_code_objects_are_gfx950():
