@@ -417,7 +417,6 @@ int enqueue_extract(vo_ctx* c, const uint8_t* img0, size_t frame_bytes, int f0, 
     const int scr = eq;                 // scratch copy
     const int st_nb = nb;
     d.eq = eq;
-    d.diag_f0 = f0;
     d.blurred += d.bplane * B * scr;
     d.cand += (size_t)d.cand_cap * B * scr;
     d.tilerows += (size_t)d.ntiles * 16 * B * scr;
@@ -425,7 +424,6 @@ int enqueue_extract(vo_ctx* c, const uint8_t* img0, size_t frame_bytes, int f0, 
     d.selbits += ((size_t)d.cand_cap / 64 + 1) * B * scr;
     d.selctl += B * scr;
     d.hist += (size_t)VO_HIST_BINS * B * scr;
-    if (d.tile_ck) d.tile_ck += (size_t)d.ntiles * B * scr;
     if (st_nb > 0) timed(c, ev, 0, q, [&] { vo::launch_stencil(d, img0, frame_bytes, st_nb, 0, q); });
     if (ev_stencil) HIPCHK(hipEventRecord(ev_stencil, q));
     timed(c, ev, 1, q, [&] { vo::launch_select(d, f0, nb, -1, q); });
@@ -563,8 +561,7 @@ void enqueue_pass(vo_ctx* c, VoFrameOut* out, int out_base, EvRec* ev, int gmax,
     // pipelined: the later hypothesis chunks run on the fit queue, after the first chunk's replay,
     // so the next pass's match and first chunk overlap them (the pass's buffer set is its own; the
     // reference-sampler mode's sample table is not, so it keeps every chunk on the pose queue)
-    static const bool split_env = !(getenv("VO_RANSAC_SPLIT") && atoi(getenv("VO_RANSAC_SPLIT")) == 0);
-    const bool split = pipelined && split_env && d.rng_mode != VO_RNG_MT19937;
+    const bool split = pipelined && vo::proc_env().ransac_split && d.rng_mode != VO_RNG_MT19937;
     timed(c, ev, 4, s, [&] { vo::launch_ransac(d, 0, s, split ? 1 : 0); });
     // c->rq: the later chunks on the trajectory queue instead (the trajectory chain moves to the fit
     // queue), so the next pass's later chunks overlap this pass's refit, triangulation and finalize
@@ -613,18 +610,11 @@ void enqueue_pass(vo_ctx* c, VoFrameOut* out, int out_base, EvRec* ev, int gmax,
 // (VO_TAIL=0: the short batch).  Host streaming keeps B: its device ring slots hold B frames.
 std::vector<int> batch_schedule(int nf, int B, int first_default = 0, int cap = 0)
 {
-    static const bool env_tail = !(getenv("VO_TAIL") && atoi(getenv("VO_TAIL")) == 0);
-    // experiment knob: VO_FIRST = size of the first batch (pipeline fill), default B
-    static const int env_first = getenv("VO_FIRST") ? atoi(getenv("VO_FIRST")) : -1;
-    // experiment knob: VO_LAST = size of the batches the chunk's last B frames are split into (the
-    // drain: the last pass covers only the last small batch)
-    static const int env_last = getenv("VO_LAST") ? atoi(getenv("VO_LAST")) : 0;
-    const int first = env_first >= 0 ? env_first : first_default;
+    const bool tail = vo::proc_env().tail;
     std::vector<int> v;
     for (int done = 0; done < nf;) {
-        int want = (done == 0 && first > 0 && first < B) ? first : B;
-        if (env_last > 0 && env_last < B && nf - done <= B) want = env_last;
-        else if (env_tail && want == B && nf - done > B && nf - done <= cap && nf - done - B <= B / 2) want = nf - done;
+        int want = (done == 0 && first_default > 0 && first_default < B) ? first_default : B;
+        if (tail && want == B && nf - done > B && nf - done <= cap && nf - done - B <= B / 2) want = nf - done;
         v.push_back(std::min(want, nf - done));
         done += v.back();
     }
@@ -705,7 +695,7 @@ int run_chunk(vo_ctx* c, const uint8_t* img0, size_t frame_bytes, int nf, VoFram
         // queue like every later pass's (the next pass speculates on its window as on any
         // pipelined one's), so pass 1's match need not wait for them (VO_PIPE_FIRST=0: the whole
         // first pass on the pose queue)
-        static const bool pipe_first = !(getenv("VO_PIPE_FIRST") && atoi(getenv("VO_PIPE_FIRST")) == 0);
+        const bool pipe_first = vo::proc_env().pipe_first;
         enqueue_pass(c, out, out_base, ev, base + f0s[k + 1], multi && c->pipeline && (!first_pass || pipe_first),
                      host_frame, first_pass);
         first_pass = false;
@@ -920,13 +910,11 @@ int vo_create(const vo_config* cfg, vo_ctx** out)
     c->Bx = Bx;
     d.B = Bx;
     d.WB = std::min(VO_MAX_WIN, 2 * B);
-    if (getenv("VO_WIN")) d.WB = std::max(1, std::min(VO_MAX_WIN, atoi(getenv("VO_WIN"))));
     d.gridw = d.WB;
     d.single = 0;
     d.gmax = INT_MAX;
     d.W = W; d.H = H; d.N = N;
-    d.ring = VO_RING_DEFAULT;
-    if (getenv("VO_RING_SLOTS")) d.ring = std::max(2 * VO_MAX_BATCH, std::min(1 << 16, atoi(getenv("VO_RING_SLOTS"))));
+    d.ring = vo_env_int("VO_RING_SLOTS", VO_RING_DEFAULT, 2 * VO_MAX_BATCH, 1 << 16);
     d.nms_k = k.nms_k; d.brow = k.border_row; d.bcol = k.border_col;
     d.resp_thr = k.resp_thr * (float)VO_RESP_SCALE;   // the stencil's responses carry VO_RESP_SCALE
     std::memcpy(&d.thr_bits, &d.resp_thr, 4);
@@ -947,29 +935,30 @@ int vo_create(const vo_config* cfg, vo_ctx** out)
     d.cand_cap = (uint32_t)ntiles * VO_TILE_CAP;
     int rc = VO_OK;
     auto bail = [&](int r) { vo_destroy(c); return r; };
-    c->serial = getenv("VO_SERIAL") && atoi(getenv("VO_SERIAL")) != 0;
+    c->serial = vo_env_flag("VO_SERIAL", false);
     // the pose queue waits for extract batches on events by default (barrier packets the queue
     // processes itself); VO_EVENT_WAIT=0: a one-wave kernel on the pose queue polls the counter
     // describe publishes, so the extract queue records no event (k_wait_ext)
-    c->event_wait = !(getenv("VO_EVENT_WAIT") && atoi(getenv("VO_EVENT_WAIT")) == 0);
-    d.xcd_map = getenv("VO_XCD") ? atoi(getenv("VO_XCD")) : 1;
-    c->pf_profile = getenv("VO_PF_PROFILE") && atoi(getenv("VO_PF_PROFILE")) != 0;
-    c->host_profile = getenv("VO_HOST_PROFILE") && atoi(getenv("VO_HOST_PROFILE")) != 0;
-    c->pipeline = !c->serial && !(getenv("VO_PIPELINE") && atoi(getenv("VO_PIPELINE")) == 0);
-    c->slack = getenv("VO_SLACK") ? std::max(0, std::min(64, atoi(getenv("VO_SLACK")))) : VO_SLACK_DEFAULT;
-    d.fault_inject = getenv("VO_FAULT_INJECT") && atoi(getenv("VO_FAULT_INJECT")) != 0;   // tests only
-    d.spin_limit = getenv("VO_SPIN_LIMIT") ? (unsigned)atoi(getenv("VO_SPIN_LIMIT")) : (1u << 22);   // tests only
+    c->event_wait = vo_env_flag("VO_EVENT_WAIT", true);
+    d.xcd_map = vo_env_flag("VO_XCD", true);
+    c->pf_profile = vo_env_flag("VO_PF_PROFILE", false);
+    c->host_profile = vo_env_flag("VO_HOST_PROFILE", false);
+    c->pipeline = !c->serial && vo_env_flag("VO_PIPELINE", true);
+    c->slack = vo_env_int("VO_SLACK", VO_SLACK_DEFAULT, 0, 64);
+    d.fault_inject = vo_env_flag("VO_FAULT_INJECT", false);   // tests only
+    // (tests only; at most 1 << 25: k_wait_ext polls spin_limit << 6 times, which must not wrap)
+    d.spin_limit = (unsigned)vo_env_int("VO_SPIN_LIMIT", 1 << 22, 0, 1 << 25);
     // the per-frame call's select in one launch (VO_SEL_FUSED=0: two launches).  With acquire polls it
     // was slower (21.2 us against 9.0 + 9.2 us, gpurun_out r5e: each poll invalidated the XCD's L2);
     // with relaxed polls the call is 1.5-1.9 us faster per frame (two alternating pairs, r5i)
-    d.sel_fused = !(getenv("VO_SEL_FUSED") && atoi(getenv("VO_SEL_FUSED")) == 0);
-    d.ransac_fused = !(getenv("VO_RANSAC_FUSED") && atoi(getenv("VO_RANSAC_FUSED")) == 0);
+    d.sel_fused = vo_env_flag("VO_SEL_FUSED", true);
+    d.ransac_fused = vo_env_flag("VO_RANSAC_FUSED", true);
     // a pipelined pass's later RANSAC chunks on the trajectory queue and the trajectory chain on the
     // fit queue (VO_RANSAC_Q=0: the chunks on the fit queue, the chain on its own queue): 0.12
     // m/frame 168.0-168.6k -> 177.6-186.1k, KITTI within noise (three alternating pairs, r5z)
-    c->rq = !(getenv("VO_RANSAC_Q") && atoi(getenv("VO_RANSAC_Q")) == 0);
+    c->rq = vo_env_flag("VO_RANSAC_Q", true);
     // repair windows hold two work records per frame (k_finalize): at most WB / 2 frames
-    d.repair_win = std::max(1, std::min(d.WB / 2, getenv("VO_REPAIR_WIN") ? atoi(getenv("VO_REPAIR_WIN")) : VO_REPAIR_WIN_DEFAULT));
+    d.repair_win = std::max(1, std::min(d.WB / 2, VO_REPAIR_WIN_DEFAULT));
     // four queues: pose (c->s), trajectory (c->st), fit (c->sf), extract (c->se[0]) -- a process has four
     // hardware queues (GPU_MAX_HW_QUEUES); a fifth stream would share one and serialise behind its kernels
     auto make_stream = [&](hipStream_t* q) { return hipStreamCreateWithFlags(q, hipStreamNonBlocking); };
@@ -992,10 +981,10 @@ int vo_create(const vo_config* cfg, vo_ctx** out)
     // frame below (KITTI's 552 tiles: 0.45 vs 0.48 us/frame, 281-285k vs 276-277k frames/s);
     // VO_SEL1=1 / 0 forces the single-workgroup / banded form.  A band too large for LDS: single.
     d.sel_emit_lds = vo::select_emit_lds_bytes(W, H);
-    d.sel1 = getenv("VO_SEL1") ? atoi(getenv("VO_SEL1")) != 0 : ntiles < VO_SEL_BANDED_TILES;
+    d.sel1 = vo_env_flag("VO_SEL1", ntiles < VO_SEL_BANDED_TILES);
     if (d.sel_emit_lds < 0) d.sel1 = 1;
     // the fused select with its band's keys staged in LDS (VO_SEL_EARLY=0: the emit after the wait)
-    if (d.sel_fused && !(getenv("VO_SEL_EARLY") && atoi(getenv("VO_SEL_EARLY")) == 0) && d.sel_emit_lds >= 0 &&
+    if (d.sel_fused && vo_env_flag("VO_SEL_EARLY", true) && d.sel_emit_lds >= 0 &&
         vo::select_fused_lds_bytes(W, H) > 0)
         d.sel_fused = 2;
     const size_t np = (size_t)W * H;
@@ -1039,15 +1028,8 @@ int vo_create(const vo_config* cfg, vo_ctx** out)
     rc |= dalloc_rec(c, "ctr", &d.ctr, VO_CTR_WORDS);
     rc |= dalloc_rec(c, "trec", &d.trec, VO_SLOTS);
     rc |= dalloc_rec(c, "plog", &d.plog, VO_PLOG);
-#if defined(VO_STAMPS) || (defined(MM_VERIFY) && MM_VERIFY) || ST_DIAG
-    rc |= dalloc_rec(c, "dbg", &d.dbg, (size_t)d.max_hyp * 16);   // stamps / diagnostic counters (words 6000..6003)
-#endif
-#if ST_DIAG
-    rc |= dalloc_rec(c, "tile_ck", &d.tile_ck, (size_t)ntiles * Bx * VO_EXT_QUEUES);
-    rc |= dalloc_rec(c, "diag_tile", &d.diag_tile, (size_t)ntiles * VO_DIAG_FRAMES);
-    rc |= dalloc_rec(c, "diag_src", &d.diag_src, (size_t)ntiles * VO_DIAG_FRAMES);
-    rc |= dalloc_rec(c, "diag_resp", &d.diag_resp, (size_t)ntiles * VO_DIAG_FRAMES);
-    rc |= dalloc_rec(c, "diag_keys", &d.diag_keys, (size_t)VO_DIAG_KEYS * VO_DIAG_FRAMES);
+#ifdef VO_STAMPS
+    rc |= dalloc_rec(c, "dbg", &d.dbg, (size_t)d.max_hyp * 16);   // stamps
 #endif
     if (rc != VO_OK) return bail(VO_ERR_HIP);
     const auto tabp = maxit_table(N, k.ransac_p);
@@ -1062,7 +1044,7 @@ int vo_create(const vo_config* cfg, vo_ctx** out)
     // batched calls: the pose rows and the commit point straight into pinned host memory (VO_OUT_ZC=0:
     // device rows and two D2H copies after the last pass, ~25 us at the end of every call, traces tr012c, trkitti)
     d.lo_host_dev = nullptr;
-    c->out_zc = !(getenv("VO_OUT_ZC") && atoi(getenv("VO_OUT_ZC")) == 0);
+    c->out_zc = vo_env_flag("VO_OUT_ZC", true);
     if (c->out_zc && hipHostGetDevicePointer((void**)&d.lo_host_dev, c->lo_host, 0) != hipSuccess) {
         (void)hipGetLastError();
         d.lo_host_dev = nullptr;
@@ -1100,7 +1082,7 @@ void vo_destroy(vo_ctx* c)
     void* ptrs[] = {d.frame_in, d.blurred, d.response, d.cand, d.tilerows, d.ckeys, d.selbits, d.hist, d.selctl, d.ext_n, d.ext_st, (void*)d.seq_starts,
                     d.kps, d.desc, d.pre, d.match_j, d.match_pairs, d.pts, d.hypF, d.counts, d.inl, d.inlmask,
                     d.model_p, d.work, d.st, (void*)d.gt, c->tab_dev, c->out_dev, d.ctr, d.trec, d.plog, d.dbg,
-                    d.plan, d.snap, d.tile_ck, d.diag_tile, d.diag_src, d.diag_resp, d.diag_keys, d.samples};
+                    d.plan, d.snap, d.samples};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (c->out_host) (void)hipHostFree(c->out_host);
@@ -1294,7 +1276,7 @@ int vo_response(vo_ctx* c, const uint8_t* gray, size_t stride, float* R)
     if (rc) return rc;
     const size_t np = (size_t)c->cfg.width * c->cfg.height;
     HIPCHK(hipMemsetAsync(c->d.response, 0, np * sizeof(float), c->s));
-    vo::launch_stencil(c->d, c->d.frame_in, 0, 1, getenv("VO_DBG") ? atoi(getenv("VO_DBG")) : 1, c->s);
+    vo::launch_stencil(c->d, c->d.frame_in, 0, 1, vo_env_int("VO_DBG", 1), c->s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(R, c->d.response, np * sizeof(float), hipMemcpyDeviceToHost, c->s));
     // the stencil histogram is consumed by select; nothing selects here, so clear it
@@ -1496,10 +1478,10 @@ int vo_process_frame(vo_ctx* c, const uint8_t* gray, size_t stride, double pose_
     // upload kernel copying it to device memory first (1.8-4.7 us less per call in four alternating
     // pairs, gpurun_out pf_a / pf_z); the next call's staging copy waits for this one (upload_frame's
     // sync).  VO_PF_ZEROCOPY=0: the upload kernel
-    static const bool zc = !(getenv("VO_PF_ZEROCOPY") && atoi(getenv("VO_PF_ZEROCOPY")) == 0);
+    const bool zc = vo::proc_env().pf_zerocopy;
     // a caller frame already in pinned host memory (vo_host_alloc / hipHostRegister) with rows
     // packed: the stencil reads it where it lies, no staging copy (VO_PF_PINNED_DIRECT=0: staged)
-    static const bool direct_ok = !(getenv("VO_PF_PINNED_DIRECT") && atoi(getenv("VO_PF_PINNED_DIRECT")) == 0);
+    const bool direct_ok = vo::proc_env().pf_pinned_direct;
     const uint8_t* src = nullptr;
     if (gray && zc && direct_ok && (stride == 0 || stride == (size_t)c->cfg.width)) {
         hipPointerAttribute_t a;
@@ -1522,7 +1504,7 @@ int vo_process_frame(vo_ctx* c, const uint8_t* gray, size_t stride, double pose_
     const int f = c->fidx;
     // one frame: extract on the pose queue, a window of one (no speculation)
     // the frame's output row straight into pinned host memory (VO_PF_OUT_ZC=0: a device row and a copy)
-    static const bool out_zc = !(getenv("VO_PF_OUT_ZC") && atoi(getenv("VO_PF_OUT_ZC")) == 0);
+    const bool out_zc = vo::proc_env().pf_out_zc;
     VoFrameOut* out = out_zc && c->out_host_dev ? c->out_host_dev : c->out_dev;
     int rc = run_chunk(c, src, 0, 1, out, f, nullptr, true);
     if (rc) return rc;
@@ -1587,7 +1569,7 @@ int run_frames(vo_ctx* c, const uint8_t* dev, const uint8_t* host, bool pinned, 
     rc = finish_timing(c, evp);
     if (rc) return rc;
     // diagnostic (VO_PLAN_DUMP=1): each pose pass of the call as (first frame, frames committed)
-    static const bool plan_dump = getenv("VO_PLAN_DUMP") && atoi(getenv("VO_PLAN_DUMP")) != 0;
+    const bool plan_dump = vo::proc_env().plan_dump;
     if (plan_dump && c->npass > pass0 && c->npass - pass0 <= VO_PLOG) {
         std::vector<int2> lg(VO_PLOG);
         HIPCHK(hipMemcpy(lg.data(), c->d.plog, sizeof(int2) * VO_PLOG, hipMemcpyDeviceToHost));
@@ -1645,7 +1627,7 @@ int vo_process_frames_host(vo_ctx* c, const uint8_t* frames, size_t frame_bytes,
     if (nframes == 0) return VO_OK;
     bool pinned = is_pinned(frames), registered = false;
     // VO_HOST_STAGING=1: never register pageable sources (tests the staging ring)
-    const bool staging_only = getenv("VO_HOST_STAGING") && atoi(getenv("VO_HOST_STAGING")) != 0;
+    const bool staging_only = vo_env_flag("VO_HOST_STAGING", false);
     if (!pinned && !staging_only) {
         // pageable: pin the call's frames for DMA (one registration per call), else stage them
         void* p = const_cast<uint8_t*>(frames);
@@ -1808,8 +1790,6 @@ int vo_debug_stamps(vo_ctx* c, unsigned long long* out, int n)
     return m;
 }
 
-// diagnostics (tools/det_stress.py): the ring slots of frames [f0, f0 + n) as the last call left
-// them -- keypoint counts, keypoints (n x N int2) and 32-test prefixes (n x N u32)
 // device buffer i of the context (name, address, bytes), i = 0 .. count - 1; returns the count
 // (i out of range: only the count).  Diagnostics: which buffer a device address falls in.
 extern "C" int vo_debug_layout(vo_ctx* c, int i, const char** name, uint64_t* ptr, uint64_t* bytes)
@@ -1824,21 +1804,8 @@ extern "C" int vo_debug_layout(vo_ctx* c, int i, const char** name, uint64_t* pt
     return n;
 }
 
-// ST_DIAG builds: rows [f0, f0 + n) of diagnostic array `what` (0 diag_tile, 1 diag_src, 2 diag_resp:
-// ntiles words per frame; 3 diag_keys: VO_DIAG_KEYS words per frame).  Returns the words per frame.
-extern "C" int vo_debug_diag(vo_ctx* c, int what, int f0, int n, unsigned long long* out)
-{
-    if (!c) return VO_ERR_ARG;
-    const VoDev& d = c->d;
-    unsigned long long* src[4] = {d.diag_tile, d.diag_src, d.diag_resp, d.diag_keys};
-    if (what < 0 || what > 3 || !src[what]) return 0;
-    const size_t per = what == 3 ? (size_t)VO_DIAG_KEYS : (size_t)d.ntiles;
-    if (f0 < 0 || n < 0 || f0 + n > VO_DIAG_FRAMES) return VO_ERR_ARG;
-    SYNC_ALL(c);
-    if (out && n) HIPCHK(hipMemcpy(out, src[what] + (size_t)f0 * per, per * n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return (int)per;
-}
-
+// diagnostics (tools/det_stress.py): the ring slots of frames [f0, f0 + n) as the last call left
+// them -- keypoint counts, keypoints (n x N int2) and 32-test prefixes (n x N u32)
 extern "C" int vo_debug_ring(vo_ctx* c, int f0, int n, int32_t* nk, int32_t* kps, uint32_t* pre)
 {
     if (!c || f0 < 0 || n <= 0 || n > c->d.ring || !nk || !kps || !pre) return VO_ERR_ARG;

@@ -40,15 +40,11 @@
 //   gt          f64 12*gt_cap      ground-truth rows for the GT scale
 //   out         VoFrameOut per frame of a call
 #pragma once
+#include <limits.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define VO_HIST_BINS 4096
-#ifndef ST_DIAG
-#define ST_DIAG 0          // diagnostic build: 1 select archives each frame's key list and per-tile checksums;
-                           // 2 + the stencil's own per-tile key / source / response checksums (d.tile_ck, d.dbg 24000..)
-#endif
-#define VO_DIAG_FRAMES 4096
-#define VO_DIAG_KEYS 8192
 #ifndef VO_SEL_BANDS
 #define VO_SEL_BANDS 8     // select workgroups per frame: bands of tile rows (k_select_count / k_select_emit)
 #endif
@@ -253,13 +249,13 @@ struct VoDev {
     int maxit_initial;
     int max_hyp;
     int B;                // extract batch capacity (frames)
-    int WB;               // pose window capacity (frames): min(2 B, VO_MAX_WIN), VO_WIN overrides
+    int WB;               // pose window capacity (frames): min(2 B, VO_MAX_WIN)
     int gridw;            // window records a pose-pass launch covers (blockIdx.y): WB; 2 for the single-frame call
     int single;           // the single-frame call (vo_process_frame): latency-shaped launches
     int gmax;             // pose pass: frames < gmax are extracted (the pass's wait covers them)
     int eq;               // extract queue of this launch (its scratch copy and counters)
     int xcd_map;          // extract kernels place a frame's workgroups on one XCD (VO_XCD=0: off)
-    int repair_win;       // window after a pass whose commit stopped early (VO_REPAIR_WIN, default VO_REPAIR_WIN_DEFAULT)
+    int repair_win;       // window after a pass whose commit stopped early (VO_REPAIR_WIN_DEFAULT, at most WB / 2)
     uint64_t seed;
     double K[9];
     uint32_t cand_cap;    // per frame
@@ -318,17 +314,11 @@ struct VoDev {
     VoPlan* plan;         // x VO_PASS_RING
     VoSnap* snap;         // x VO_PASS_RING
     unsigned long long* dbg;   // diagnostic s_memtime stamps (VO_STAMPS builds only)
-    unsigned long long* tile_ck;   // ST_DIAG builds: x B x VO_EXT_QUEUES, per tile the stencil's key checksum
-    // ST_DIAG builds, per frame f < VO_DIAG_FRAMES of the call (frame index since vo_reset):
-    unsigned long long* diag_tile;   // [f][tile]  select: checksum of the tile's keys as read
-    unsigned long long* diag_src;    // [f][tile]  stencil: checksum of the source rows a wave consumed (even tiles)
-    unsigned long long* diag_resp;   // [f][tile]  stencil: checksum of the responses a wave computed (even tiles)
-    unsigned long long* diag_keys;   // [f][VO_DIAG_KEYS] select: the frame's compact key list (first VO_DIAG_KEYS)
-    int diag_f0;                     // frame index of batch frame 0 (enqueue_extract)
     int fault_inject;                // VO_FAULT_INJECT=1 (tests only): launch_stencil adds N counts to each frame's
                                      // top histogram bin, so the select's consistency check must fire
     unsigned spin_limit;             // polls of the fused select's / fused RANSAC's bounded waits (1 << 22;
-                                     // VO_SPIN_LIMIT=0, tests only: every wait times out at once)
+                                     // VO_SPIN_LIMIT=0, tests only: every wait times out at once); at most
+                                     // 1 << 25, so k_wait_ext's spin_limit << 6 cannot wrap
 };
 
 // launch wrappers (vo_kernels.hip)
@@ -344,7 +334,45 @@ __host__ __device__ inline size_t vo_pts32_index(int i, int c)
 // pts32 entries per frame record: whole words
 #define VO_PTS32_PER(N) ((size_t)(((N) + 63) / 64) * 256)
 
+// Environment knobs (INTEGRATION.md lists them).  An unset or empty variable gives def; a value is
+// parsed once with strtol and clamped to [lo, hi].
+inline int vo_env_int(const char* name, int def, int lo = INT_MIN, int hi = INT_MAX)
+{
+    const char* e = getenv(name);
+    if (!e || !*e) return def;
+    const long v = strtol(e, nullptr, 10);
+    return (int)(v < lo ? lo : v > hi ? hi : v);
+}
+inline bool vo_env_flag(const char* name, bool def) { return vo_env_int(name, def ? 1 : 0) != 0; }
+
+// The knobs read once per process (every other knob is read per context, in vo_create, or per call).
+struct VoProcEnv {
+    // launch wrappers (vo_kernels.hip)
+    bool st_flat;            // VO_ST_FLAT: the FLAT stencil form where the NMS margins allow it
+    int sel_small;           // VO_SEL_SMALL: batches up to this many frames use the banded select
+    int stseg;               // VO_STSEG: stencil tiles per wave segment (4 / 5 / 6 / 8)
+    int pf_segt;             // VO_PF_SEGT: the per-frame call's segment, 1 / 2 / 4 tile rows
+    bool stseg_adapt;        // VO_STSEG_ADAPT: shorter segments for small batches
+    int sel_lds_kb;          // VO_SEL_LDS_KB: k_select's dynamic LDS request
+    bool ds_lds_table;       // VO_DS_LDS_TABLE: the per-frame describe reads its pair table from LDS
+    bool ds_pf;              // VO_DS_PF: the per-frame call's eight-wave describe
+    bool ransac_wave_hyp;    // VO_RANSAC_WAVE_HYP: fused RANSAC with one hypothesis per wave
+    int hyp_cuts[14];        // VO_HYP_CUTS: the cuts after [0, VO_HYP_CHUNK0), ascending
+    int n_hyp_cuts;
+    int rreps;               // VO_RREPS: hypotheses per wave in the last chunk
+    int tri_bpf;             // VO_TRI_BPF: triangulation workgroups per frame
+    // host driver (vo_api.cpp)
+    bool ransac_split;       // VO_RANSAC_SPLIT: a pipelined pass's later chunks off the pose queue
+    bool tail;               // VO_TAIL: a short remainder joins the last full batch
+    bool pipe_first;         // VO_PIPE_FIRST: a chunk's first pass pipelined like the later ones
+    bool pf_zerocopy;        // VO_PF_ZEROCOPY: the per-frame call's stencil reads the pinned frame
+    bool pf_pinned_direct;   // VO_PF_PINNED_DIRECT: ... where the caller's frame lies (no staging copy)
+    bool pf_out_zc;          // VO_PF_OUT_ZC: the per-frame call's output row into pinned host memory
+    bool plan_dump;          // VO_PLAN_DUMP: print each pose pass of a call (diagnostic output only)
+};
+
 namespace vo {
+const VoProcEnv& proc_env();   // filled from the environment at its first call (vo_kernels.hip)
 // extract of nb frames: frame f0 + z reads img0 + z * frame_bytes into slot
 // (slot_override >= 0 ? slot_override : (f0 + z) % VO_RING), scratch z.  publish > 0: the
 // last describe workgroup stores it to ctr[VO_SYNC_EXT] for the pose queue

@@ -14,7 +14,6 @@
 #include <utility>
 #include <cstdio>
 #include <cstdlib>
-#include <vector>
 
 #include "vo_internal.h"
 #include "vo_sampson32.h"
@@ -46,8 +45,7 @@ constexpr int ds_onpad()                            // sum over p of ceil((42 - 
 }
 #define DS_ONPAD (ds_onpad())
 __constant__ float4 c_orient[DS_ONPAD];
-// the same entries unpadded, in pair order (the fully unrolled describe, DS_UNROLL), plus one
-// block of zeros read by the last block's prefetch
+// the same entries unpadded, in pair order (k_describe_pf's term waves), plus one block of zeros
 #ifndef DS_UB
 #define DS_UB 8                // terms per block of the unrolled sum (one table request per block)
 #endif
@@ -55,15 +53,9 @@ __constant__ float4 c_orient_u[VO_FREAK_NPAIRS + DS_UB];
 // the pattern points (x, y) and the pair list (p, q) in pair order (k_describe_pf's loop indices)
 __constant__ short2 c_ppt[VO_FREAK_NPOINTS];
 __constant__ uchar2 c_pair[VO_FREAK_NPAIRS];
-// k_describe_pf's term tables, padded to whole 64-term chunks (padding: both rows 0, weights 0):
-// each entry one scalar load -- the pair as the two sample rows' LDS byte offsets (p * 256 |
-// q * 256 << 16), the weights as in c_orient_u
 #ifndef DP_CHUNK
 #define DP_CHUNK 96                    // k_describe_pf: terms per chunk of its LDS ring (64: 1.3-2.6 us slower per call, r5q)
 #endif
-#define DP_NPAD (((VO_FREAK_NPAIRS + DP_CHUNK - 1) / DP_CHUNK) * DP_CHUNK)
-__constant__ uint32_t c_pairoff[DP_NPAD];
-__constant__ float4 c_orient_pf[DP_NPAD];
 
 static bool g_tables_ready = false;
 static void ensure_tables()
@@ -97,14 +89,6 @@ static void ensure_tables()
     for (int t = 0; t < VO_FREAK_NPAIRS; ++t) pair[t] = make_uchar2(pp[t], pq[t]);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(c_ppt), ppt, sizeof(ppt));
     (void)hipMemcpyToSymbol(HIP_SYMBOL(c_pair), pair, sizeof(pair));
-    static uint32_t pairoff[DP_NPAD];
-    static float4 orient_pf[DP_NPAD];
-    for (int t = 0; t < DP_NPAD; ++t) {
-        pairoff[t] = t < VO_FREAK_NPAIRS ? (uint32_t)pp[t] * 256u | ((uint32_t)pq[t] * 256u) << 16 : 0u;
-        orient_pf[t] = t < VO_FREAK_NPAIRS ? orient_u[t] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(c_pairoff), pairoff, sizeof(pairoff));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(c_orient_pf), orient_pf, sizeof(orient_pf));
     g_tables_ready = true;
 }
 
@@ -414,28 +398,6 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 #define ST_TW VO_TILE_W                // tile width: 57 (56: 12 strips per KITTI row instead of 11; 48: 1080p -3 %)
 #define ST_TH VO_TILE_H                // tile height (select reads 16 row counts per tile)
 #define ST_SW VO_STRIP_W               // strip width = two tiles: 114 output columns per wave
-#ifndef ST_RSEL_ASM
-#define ST_RSEL_ASM 1                  // the response's rounding selects ordered by hand (no s_nop)
-#endif
-#ifndef ST_SOFF_HOIST
-#define ST_SOFF_HOIST 1                // a row group's source-row offsets read into SGPRs before its rows
-#endif
-#ifndef ST_NODOT
-#define ST_NODOT 0                     // diagnostic: the horizontal blur without v_dot2_u32_u16
-#endif
-#ifndef ST_LTMASK_ASM
-#define ST_LTMASK_ASM 1                // the NMS maxima's lane masks straight from an asm v_cmp
-#endif
-#ifndef ST_GRAD_DPP
-#define ST_GRAD_DPP (!ST_SHIFT_BPERM)  // the gradients' neighbour columns as DPP operands (not the FLAT form's shifts)
-#endif
-#ifndef ST_DPP_ADD
-#define ST_DPP_ADD 1                   // box sums with v_add_f32_dpp (0: v_mov_b32_dpp + packed adds)
-#endif
-#ifndef ST_PF_BPERM
-#define ST_PF_BPERM 1                  // one-tile-row segments: a row's 128 source bytes by two 64-byte loads and
-                                       // two ds_bpermute (instead of two overlapping 128-byte loads)
-#endif
 #define ST_HALO 7                      // blur 3 + gradient 1 + window 2 + nms 1
 #define ST_TCAP VO_TILE_CAP            // candidates per tile (strict maxima: at most one per 2x2 cell)
 #ifndef ST_SEGT_DEFAULT
@@ -447,20 +409,16 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 static_assert(ST_SW + 2 * ST_HALO <= 128, "strip + halo within one wave of column pairs");
 static_assert(VO_STRIP_XL + ST_TW - 1 == 63, "tile A in lanes 0..31, tile B in lanes 32..63");
 
-#ifndef ST_NOPK
-#define ST_NOPK 1                      // k_stencil without packed FP32 (every v_pk_*_f32 split in two v_*_f32):
-                                       // the instruction class round 4 saw perturbed next to its MFMA matcher
-                                       // (DESIGN.md section 3); four alternating pairs, round 5 (gpurun_out
-                                       // r5c_ab): 289.6k with packed FP32, 291.1k without -- within noise, so
-                                       // the stencil ships without it (0: the packed form, ST_XSUB_ASM)
-#endif
-// ST_NOPK: the stencil and every helper it inlines (to the end of k_stencil) compiled without packed
+// k_stencil ships without packed FP32 (every v_pk_*_f32 split in two v_*_f32): the instruction class
+// round 4 saw perturbed next to its MFMA matcher; four alternating pairs in
+// round 5 measured 289.6k frames/s with packed FP32 and 291.1k without -- within noise.
+// The stencil and every helper it inlines (to the end of k_stencil) are compiled without packed
 // FP32 -- the whole region, so the kernel's callees keep a subset of its target features and inline
-#if ST_NOPK && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute push (__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
 // bit casts, popcount and the histogram atomic as the stencil's own inline helpers (the HIP header's
-// are defined outside the ST_NOPK region, so a no-packed-FP32 stencil could not inline them)
+// are defined outside the no-packed-FP32 region, so the stencil could not inline them)
 __device__ __forceinline__ int st_popc(unsigned long long v) { return __builtin_popcountll(v); }
 __device__ __forceinline__ int st_f2i(float v) { return __builtin_bit_cast(int, v); }
 __device__ __forceinline__ float st_i2f(int v) { return __builtin_bit_cast(float, v); }
@@ -478,47 +436,16 @@ __device__ __forceinline__ int refl101(int i, int n)
 // read of a lane that is off in EXEC returns 0, so the shift must run with the whole wave on:
 // the empty volatile asm pins it where it is written (the compiler otherwise sank a shift into
 // the masked arm of a select, and border lanes read 0 from their masked neighbours).
-#ifndef VO_DPP_PIN
-#define VO_DPP_PIN 1
-#endif
-#ifndef ST_DPP_NOP
-#define ST_DPP_NOP 0                   // diagnostic: wait states before every wave shift
-#endif
-#ifndef ST_SHIFT_BPERM
-#define ST_SHIFT_BPERM 0               // diagnostic: wave shifts through ds_bpermute instead of DPP
-#endif
-__device__ __forceinline__ int shift_bperm(int v, int d)
-{
-    const int l = (int)(threadIdx.x & 63), src = l + d;
-    const int r = __builtin_amdgcn_ds_bpermute(src << 2, v);
-    return (src < 0 || src > 63) ? 0 : r;
-}
 __device__ __forceinline__ int from_left(int v)
 {
-#if ST_SHIFT_BPERM
-    return shift_bperm(v, -1);
-#endif
-#if ST_DPP_NOP
-    asm volatile("s_nop %c1" : "+v"(v) : "i"(ST_DPP_NOP - 1));
-#endif
     int r = __builtin_amdgcn_mov_dpp(v, 0x138, 0xf, 0xf, true);   // bound_ctrl: edge lanes read 0, no old operand
-#if VO_DPP_PIN
     asm volatile("" : "+v"(r));
-#endif
     return r;
 }
 __device__ __forceinline__ int from_right(int v)
 {
-#if ST_SHIFT_BPERM
-    return shift_bperm(v, 1);
-#endif
-#if ST_DPP_NOP
-    asm volatile("s_nop %c1" : "+v"(v) : "i"(ST_DPP_NOP - 1));
-#endif
     int r = __builtin_amdgcn_mov_dpp(v, 0x130, 0xf, 0xf, true);   // bound_ctrl: edge lanes read 0, no old operand
-#if VO_DPP_PIN
     asm volatile("" : "+v"(r));
-#endif
     return r;
 }
 
@@ -566,23 +493,6 @@ typedef float st_f2 __attribute__((ext_vector_type(2)));
 typedef unsigned short st_w2 __attribute__((ext_vector_type(2)));
 // (the box sums add across lanes with hand-written v_add_f32_dpp in k_stencil: the build disables
 // LLVM's DPP combine -- it mis-folded a wave shift into v_subrev_u32_dpp on gfx950, Makefile)
-__device__ __forceinline__ float from_leftf(float v) { return st_i2f(from_left(st_f2i(v))); }
-__device__ __forceinline__ float from_rightf(float v) { return st_i2f(from_right(st_f2i(v))); }
-// (a.x - b.y, b.x - a.y) in one v_pk_add_f32: cross halves through op_sel, signs through neg
-#ifndef ST_XSUB_ASM
-#define ST_XSUB_ASM (!ST_NOPK)         // (the asm form is a v_pk_add_f32)
-#endif
-
-__device__ __forceinline__ st_f2 st_xsub(st_f2 a, st_f2 b)
-{
-#if ST_XSUB_ASM
-    st_f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[1,0]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-#else
-    return st_f2{a.x - b.y, b.x - a.y};
-#endif
-}
 __device__ __forceinline__ st_f2 st_fma(st_f2 a, st_f2 b, st_f2 c) { return __builtin_elementwise_fma(a, b, c); }
 // the pair's response, kernel .c:108-114 (f32, in the reference's order): det = (jx2 jy2) -
 // (sxy sxy); (tr tr) - 4 det as one fma (4 det is exact); (tr * 0.5) - (0.5 * s) == 0.5 * (tr - s)
@@ -601,7 +511,6 @@ __device__ __forceinline__ st_f2 st_response2(st_f2 jx2, st_f2 jy2, st_f2 sxy)
     const st_f2 sp = {st_i2f(st_f2i(s.x) + 1), st_i2f(st_f2i(s.y) + 1)};
     const st_f2 rm = st_fma(-sm, s, x), rp = st_fma(-sp, s, x);
     st_f2 r;
-#if ST_RSEL_ASM
     // r = rp > 0 ? sp : (rm <= 0 ? sm : s) per component (NaN: s), the four compares into SGPR
     // pairs first, so every select reads a mask written two or more instructions earlier (left to
     // itself LLVM pairs each compare with its select through VCC and pads it with s_nop 1)
@@ -622,10 +531,6 @@ __device__ __forceinline__ st_f2 st_response2(st_f2 jx2, st_f2 jy2, st_f2 sxy)
             : [rmx] "v"(rm.x), [rmy] "v"(rm.y), [rpx] "v"(rp.x), [rpy] "v"(rp.y), [sx] "v"(s.x), [sy] "v"(s.y),
               [smx] "v"(sm.x), [smy] "v"(sm.y), [spx] "v"(sp.x), [spy] "v"(sp.y));
     }
-#else
-    r.x = rp.x > 0.0f ? sp.x : (rm.x <= 0.0f ? sm.x : s.x);
-    r.y = rp.y > 0.0f ? sp.y : (rm.y <= 0.0f ? sm.y : s.y);
-#endif
 #if VO_RESP_SCALE == 2
     return tr - r;                    // twice the response (exact): see VO_RESP_SCALE
 #else
@@ -638,36 +543,12 @@ __device__ __forceinline__ void st_for(F&& f, std::integer_sequence<int, I...>)
 {
     (f(std::integral_constant<int, I>{}), ...);
 }
-#define ST_BUF_DW3 0x00020000
+#define ST_BUF_DW3 0x00020000      // gfx9 buffer descriptor word 3 (raw bytes, no format)
 #ifndef ST_FLAT_DEFAULT
 #define ST_FLAT_DEFAULT 0     // VO_ST_FLAT=1: the branch-free FLAT form where the margins allow it (measured slower:
                               // KITTI 264k vs 283k frames/s, stencil 2.01 vs 1.81 us/frame; parity-tested as a knob)
 #endif
-#ifndef LDS_POISON
-#define LDS_POISON 0      // diagnostic build: k_select / k_describe poison their LDS first
-#endif
-#ifndef ST_DROP_SOFFSET
-#define ST_DROP_SOFFSET 0
-#endif      // gfx9 buffer descriptor word 3 (raw bytes, no format)
 
-#ifndef SL_STAGE2
-#define SL_STAGE2 1                    // k_select: two threads per tile stage its keys (eight loads in flight)
-#endif
-#ifndef ST_LHIST
-#define ST_LHIST 1                     // k_select builds the histogram from its keys; the stencil writes none
-#endif
-// WRITE_SIZE attribution probes (diagnostic builds only, tools/stencil_write_probe.py): the stencil
-// without its blurred-plane stores (1), its key and tile-row stores (2), its histogram atomics (4)
-#ifndef ST_PROBE_NOSTORE
-#define ST_PROBE_NOSTORE 0
-#endif
-#ifndef ST_HIST_FLUSH
-#define ST_HIST_FLUSH 0   // the general form's histogram counts at the group flush (from the LDS keys)
-#endif
-#ifndef ST_KEYS_LDS
-#define ST_KEYS_LDS 1     // the general form stages a tile pair's keys in LDS and writes them once per
-                          // 16-row group, contiguously (0: a divergent 8-byte global store per maximum)
-#endif
 // grid xcd_grid(ceil(waves / 4), nb): 4 waves per workgroup, one (strip, segment) per wave
 #ifndef ST_WAVES_PER_EU
 #define ST_WAVES_PER_EU 4
@@ -681,7 +562,7 @@ __device__ __forceinline__ void st_for(F&& f, std::integer_sequence<int, I...>)
 // block with no branch, and the scheduler overlaps consecutive rows' dependency chains.
 // NH: no histogram -- the batch's select is the one-workgroup k_select, which builds the histogram
 // in LDS from the keys it stages (the stencil's agent-scope histogram atomics go to memory: 232 KB of
-// WRITE per KITTI frame against a 16 KB histogram, tools/stencil_write_probe.py, r6c)
+// WRITE per KITTI frame against a 16 KB histogram, r6c)
 template <int SEGT, bool DBG, bool FLAT, bool NH = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAVES_PER_EU))) k_stencil(VoDev d, const uint8_t* __restrict__ img0, size_t frame_bytes,
                                                   int write_response, int nb)
@@ -697,11 +578,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
     if (g >= nsx * nseg) return;
     const int sxi = g % nsx, seg = g / nsx;
     const int lane = threadIdx.x & 63;
-#if ST_KEYS_LDS
     // this wave's tile pair's keys (+ 128 lane-private slots: the FLAT form's lanes without a maximum)
     __shared__ uint64_t s_keys[4][2 * ST_TCAP + (FLAT ? 128 : 0)];
     uint64_t* __restrict__ wkeys = s_keys[threadIdx.x >> 6];
-#endif
     // image rows and blurred rows through buffer descriptors: the row offset is a scalar
     // operand of the access (no per-row address arithmetic), and a lane whose offset is past
     // the plane (the halo lanes' stores) is dropped by the range check
@@ -712,16 +591,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
     uint64_t* __restrict__ cand = d.cand + (size_t)z * d.cand_cap;
     uint8_t* __restrict__ tilerows = d.tilerows + (size_t)z * d.ntiles * ST_TH;
     uint32_t* __restrict__ hist = d.hist + (size_t)z * VO_HIST_BINS;
-    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rcand =
-        __builtin_amdgcn_make_buffer_rsrc((void*)cand, 0, (int)(d.cand_cap * 8u), ST_BUF_DW3);
-    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rhist =
-        __builtin_amdgcn_make_buffer_rsrc((void*)hist, 0, VO_HIST_BINS * 4, ST_BUF_DW3);
     const int Wb = d.bstride;
     // wave shifts: pinned against sinking into a masked arm, except in the FLAT form (no masked arm)
-    auto shl = [](int v) { if constexpr (FLAT && !ST_SHIFT_BPERM) return __builtin_amdgcn_mov_dpp(v, 0x130, 0xf, 0xf, true); else return from_right(v); };
-    auto shr = [](int v) { if constexpr (FLAT && !ST_SHIFT_BPERM) return __builtin_amdgcn_mov_dpp(v, 0x138, 0xf, 0xf, true); else return from_left(v); };
-    [[maybe_unused]] auto shrf = [&](float v) { return st_i2f(shr(st_f2i(v))); };
-    [[maybe_unused]] auto shlf = [&](float v) { return st_i2f(shl(st_f2i(v))); };
+    auto shl = [](int v) { if constexpr (FLAT) return __builtin_amdgcn_mov_dpp(v, 0x130, 0xf, 0xf, true); else return from_right(v); };
+    auto shr = [](int v) { if constexpr (FLAT) return __builtin_amdgcn_mov_dpp(v, 0x138, 0xf, 0xf, true); else return from_left(v); };
 
     const int xs = sxi * ST_SW, ys = seg * SEG;
     const int c0 = xs - VO_STRIP_XL + 2 * lane;                // this lane's columns: c0, c0 + 1
@@ -763,25 +636,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
     int ru0 = 0, rm0 = 0, rd0 = 0, ru1 = 0, rm1 = 0, rd1 = 0;               // response rows (f32 bits)
     int toffA = 0, toffB = 0;                                                // candidates so far per tile
     int trows = 0;                                                           // lane r (16 + r): tile A (B) row r count
-#if ST_DIAG & 2
-    unsigned long long dck = 0ull;                                           // checksum of the keys this lane stored
-    unsigned long long sck = 0ull, rck = 0ull;                               // source rows consumed, responses computed
-    const int dfr = d.diag_f0 + z;                                           // frame index (diagnostic arrays)
-#elif ST_DIAG & 4
-    uint32_t lsck = 0u;                                                      // light: source rows consumed (one mad a row)
-    const int dfr = d.diag_f0 + z;
-#endif
 
     // lane u of the result: byte offset of source row ys - 7 + k0 + u (u < 16)
     auto row_offsets = [&](int k0) {
         const int y = refl101(ys - ST_HALO + k0 + (lane & 15), H);
         return y * W;                                          // frames < 2^31 px
     };
-#if ST_PF_BPERM
     constexpr bool BP = SEGT == 1;
-#else
-    constexpr bool BP = false;
-#endif
     // BP: lane l loads window columns l and 64 + l (one 64-byte span per load), packed as bytes 0 / 1;
     // its pair (window columns 2l, 2l + 1) comes back by two ds_bpermute and a byte select
     const int xa = refl101(xs - VO_STRIP_XL + lane, W), xb = refl101(xs - VO_STRIP_XL + 64 + lane, W);
@@ -813,11 +674,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
         constexpr int P = decltype(PH)::value;
         constexpr int r = decltype(R)::value;
         s0 = s1; s1 = s2; s2 = s3; s3 = s4; s4 = s5; s5 = s6; s6 = src;
-#if ST_DIAG & 2
-        sck += mix64((uint64_t)src ^ ((uint64_t)(uint32_t)k << 32));
-#elif ST_DIAG & 4
-        lsck = lsck * 0x01000193u + src;
-#endif
         if constexpr (P >= 1) {
             // 1. 7x7 blur (cv::GaussianBlur 8U fixed point, A.1): vertical taps on both columns
             //    in 16-bit halves (<= 65280); the horizontal taps as dot products of 16-bit pairs
@@ -830,11 +686,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
             const uint32_t V = as_u32(v);
             const uint32_t VL = (uint32_t)shr((int)V), VR = (uint32_t)shl((int)V);
             const uint32_t VL2 = (uint32_t)shr((int)VL), VR2 = (uint32_t)shl((int)VR);
-#if ST_NODOT
-            auto dot = [](uint32_t a, st_w2 w, uint32_t c) { return (a & 0xFFFFu) * (uint32_t)w.x + (a >> 16) * (uint32_t)w.y + c; };
-#else
             auto dot = [](uint32_t a, st_w2 w, uint32_t c) { return __builtin_amdgcn_udot2(as_u16x2(a), w, c, false); };
-#endif
             // column c0: 72 I(c0) + 56 (I(c0-1) + I(c0+1)) + 28 (I(c0-2) + I(c0+2)) + 8 (I(c0-3) + I(c0+3))
             const uint32_t ha = dot(VR, st_w2{28, 8}, dot(VL2, st_w2{0, 8}, dot(VL, st_w2{28, 56}, dot(V, st_w2{72, 56}, 32768u))));
             const uint32_t hb = dot(VR2, st_w2{8, 0}, dot(VR, st_w2{56, 28}, dot(VL, st_w2{8, 28}, dot(V, st_w2{56, 72}, 32768u))));
@@ -850,22 +702,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
                 // straddling store keeps its in-range lanes, nothing lands past num_records), so
                 // round 3's drop through soffset was also safe; voffset keeps the row offset in
                 // soffset a plain scalar operand.
-#if ST_DROP_SOFFSET
-                // round 3's form, kept for the A/B evidence run only (tools/gpu_det.sh): the drop in soffset
-                const int brow = k < SEG + 10 ? (ys - 10 + k) * Wb : 0x40000000;
-                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)__builtin_amdgcn_perm(hb, ha, 0x0c0c0602u), rblur, boff,
-                                                      brow, 0);
-                (void)boffq;
-#else
-                if constexpr (ST_PROBE_NOSTORE & 1) {
-                } else if constexpr (P == 5 && r >= ST_TH - 4) {
+                if constexpr (P == 5 && r >= ST_TH - 4) {
                     __builtin_amdgcn_raw_buffer_store_b16((unsigned short)__builtin_amdgcn_perm(hb, ha, 0x0c0c0602u), rblur,
                                                           boffq, (ys - 10 + k) * Wb, 0);
                 } else {
                     __builtin_amdgcn_raw_buffer_store_b16((unsigned short)__builtin_amdgcn_perm(hb, ha, 0x0c0c0602u), rblur,
                                                           boff, (ys - 10 + k) * Wb, 0);
                 }
-#endif
             }
         }
         if constexpr (P >= 2) {
@@ -873,7 +716,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
             //    the reference's f32 values are these integers (all below 2^11)
             const int yg = ys - 11 + k;
             const st_f2 DV = BA - BE, SV = st_fma(BM, st_f2{2.0f, 2.0f}, BA + BE);
-#if ST_GRAD_DPP
             // the neighbour columns' dv / sv as DPP operands of the adds and subtracts that use them
             // (the same operations on the same values as the shifted-copy form below: six VALU for
             // its four v_mov_b32_dpp and six adds / subtracts).  s_nop 1: the two wait states a DPP
@@ -892,13 +734,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
             st_f2 JX = st_fma(DV, st_f2{2.0f, 2.0f}, st_f2{a1, a2}); // (dL + 2 dv0 + dv1, dv0 + 2 dv1 + dR)
             st_f2 JY = {jy0, jy1};                                    // (sL - sv1, sv0 - sR)
             st_f2 JXY = {jxy0, jxy1};                                 // (dL - dv1, dv0 - dR)
-#else
-            const st_f2 Y = {shrf(DV.y), shlf(DV.x)};                 // dv of columns c0 - 1, c0 + 2
-            const st_f2 Z = {shrf(SV.y), shlf(SV.x)};
-            st_f2 JX = st_fma(DV, st_f2{2.0f, 2.0f}, Y + DV.yx);      // (dL + 2 dv0 + dv1, dv0 + 2 dv1 + dR)
-            st_f2 JY = st_xsub(Z, SV);                                // (sL - sv1, sv0 - sR)
-            st_f2 JXY = st_xsub(Y, DV);                               // (dL - dv1, dv0 - dR)
-#endif
             // both conditions are wave-uniform and rare (the image's outer columns and rows): the
             // empty volatile asm keeps them branches (if-converted, they cost 12 selects a row)
             if constexpr (!FLAT) {
@@ -922,7 +757,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
         if constexpr (P >= 4) {
             // horizontal 5-sums: column c0 takes c0-2 .. c0+2 = the left pair, its own pair and
             // the right lane's c0; column c0 + 1 the left lane's c0 + 1, its pair, the right pair
-#if ST_DPP_ADD
             // (exact integer sums below 2^24: the order is free) per plane four DPP adds and one add,
             // the three planes in one block ordered so that every DPP source was written at least
             // two VALU instructions earlier (the wait states a DPP read of a fresh VGPR needs; the
@@ -931,9 +765,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
             {
                 float pX, pY, pS, xX, yX, xY, yY, xS, yS;
                 asm(
-#if ST_DPP_NOP
-                    "s_nop 7\n\t"
-#endif
                     "v_add_f32 %[pX], %[ax], %[ay]\n\t"
                     "v_add_f32 %[pY], %[bx], %[by]\n\t"
                     "v_add_f32 %[pS], %[cx], %[cy]\n\t"
@@ -956,15 +787,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
                     : [ax] "v"(VX.x), [ay] "v"(VX.y), [bx] "v"(VY.x), [by] "v"(VY.y), [cx] "v"(VS.x), [cy] "v"(VS.y));
             }
             const st_f2 SX = {sx0, sx1}, SY = {sy0, sy1}, SS = {ss0, ss1};
-#else
-            auto box = [](st_f2 a) {
-                const st_f2 p = a + a.yx;                              // (a0 + a1, a0 + a1)
-                const st_f2 l = {from_leftf(p.x), from_leftf(a.y)};
-                const st_f2 r = {from_rightf(a.x), from_rightf(p.x)};
-                return (l + p) + r;
-            };
-            const st_f2 SX = box(VX), SY = box(VY), SS = box(VS);
-#endif
             // 4. response of row yr (kernel .c:108-114), 0 outside 2 <= i <= H-3, 2 <= j <= W-3
             const int yr = ys - 13 + k;
             const bool rrow = (unsigned)(yr - 2) <= (unsigned)(H - 5);
@@ -984,9 +806,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
             }
             ru0 = rm0; rm0 = rd0; rd0 = o0;
             ru1 = rm1; rm1 = rd1; rd1 = o1;
-#if ST_DIAG & 2
-            rck += mix64((((uint64_t)(uint32_t)o0 << 32) | (uint32_t)o1) ^ ((uint64_t)(uint32_t)k << 48));
-#endif
         }
         if constexpr (P >= 5) {
             // 5. strict 3x3 NMS of row yn = tile row r inside the retinal margin
@@ -1003,13 +822,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
             // rok materialised the lane bools and compared them again, 4 VALU a row); rok is
             // wave-uniform and masks them as scalars, and inside the branch it holds
             auto lt_mask = [](int a, int b) {
-#if ST_LTMASK_ASM
                 unsigned long long m;
                 asm("v_cmp_lt_i32_e64 %0, %1, %2" : "=s"(m) : "v"(a), "v"(b));
                 return m;
-#else
-                return (unsigned long long)__builtin_amdgcn_ballot_w64(a < b);
-#endif
             };
             const unsigned long long rokm = rok ? ~0ull : 0ull;      // (a select, not a branch around the compare)
             const unsigned long long b0 = lt_mask(nb0, rm0) & rokm, b1 = lt_mask(nb1, rm1) & rokm;
@@ -1018,7 +833,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
             const int cA = st_popc(b0 & mA) + st_popc(b1 & mA);
             const int cB = st_popc(b0 & mB) + st_popc(b1 & mB);
             // (readfirstlane: the counts are wave-uniform SGPR values already -- a no-op -- but the
-            // ST_NOPK build's compiler keeps them in VGPRs without it)
+            // no-packed-FP32 build's compiler keeps them in VGPRs without it)
             asm("v_writelane_b32 %0, %1, %2" : "+v"(trows) : "s"(__builtin_amdgcn_readfirstlane(cA)), "n"(r));
             asm("v_writelane_b32 %0, %1, %2" : "+v"(trows) : "s"(__builtin_amdgcn_readfirstlane(cB)), "n"(16 + r));
             if constexpr (FLAT) {
@@ -1028,28 +843,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
                                       __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u))));
                 const uint32_t base = (uint32_t)(isB ? ST_TCAP + toffB - cA : toffA) + pos0;
                 const uint32_t key_lo = ((uint32_t)yn << 16) | (uint32_t)c0;
-#if ST_KEYS_LDS
                 // every lane writes LDS: a lane without a maximum into its own slot past the pair's
                 // (the histogram counts follow from the flushed keys, once per 16-row group)
                 const int s0 = mx0 ? (int)base : 2 * ST_TCAP + lane;
                 const int s1 = mx1 ? (int)(base + (mx0 ? 1u : 0u)) : 2 * ST_TCAP + 64 + lane;
                 wkeys[s0] = ((uint64_t)(uint32_t)rm0 << 32) | key_lo;
                 wkeys[s1] = ((uint64_t)(uint32_t)rm1 << 32) | (key_lo + 1u);
-#else
-                // every lane stores; a lane without a maximum gets an out-of-range offset (dropped)
-                const uint32_t slot0 = (uint32_t)((yn / ST_TH) * ntx + 2 * sxi) * ST_TCAP + base;
-                const int o0 = mx0 ? (int)(slot0 * 8u) : 0x7FFFFFF0;
-                const int o1 = mx1 ? (int)((slot0 + (mx0 ? 1u : 0u)) * 8u) : 0x7FFFFFF0;
-                typedef unsigned int st_u2 __attribute__((ext_vector_type(2)));
-                __builtin_amdgcn_raw_buffer_store_b64(st_u2{key_lo, (uint32_t)rm0}, rcand, o0, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b64(st_u2{key_lo + 1u, (uint32_t)rm1}, rcand, o1, 0, 0);
-                const int h0 = mx0 ? (int)(min(((uint32_t)rm0 - thr_bits) >> 15, (uint32_t)(VO_HIST_BINS - 1)) * 4u) : 0x7FFFFFF0;
-                const int h1 = mx1 ? (int)(min(((uint32_t)rm1 - thr_bits) >> 15, (uint32_t)(VO_HIST_BINS - 1)) * 4u) : 0x7FFFFFF0;
-                if constexpr (!NH) {
-                    (void)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, rhist, h0, 0, 0);
-                    (void)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, rhist, h1, 0, 0);
-                }
-#endif
             } else if (b0 | b1) {
                 // tile-local raster order: rows before this one, then columns before: the lower
                 // lanes' pairs, and c0 before c0 + 1
@@ -1059,31 +858,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
                                       __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u))));
                 const uint32_t base = (uint32_t)(isB ? ST_TCAP + toffB - cA : toffA) + pos0;
                 const uint32_t key_lo = ((uint32_t)yn << 16) | (uint32_t)c0;
-#if ST_KEYS_LDS
                 uint64_t* __restrict__ tk = wkeys;
-#else
-                const int tileA = (yn / ST_TH) * ntx + 2 * sxi;
-                uint64_t* __restrict__ tk = cand + (size_t)tileA * ST_TCAP;
-#endif
                 if (mx0) {
                     tk[base] = ((uint64_t)(uint32_t)rm0 << 32) | key_lo;
-#if !(ST_KEYS_LDS && ST_HIST_FLUSH)
                     const uint32_t bin = min(((uint32_t)rm0 - thr_bits) >> 15, (uint32_t)(VO_HIST_BINS - 1));
-                    if (!(ST_PROBE_NOSTORE & 4) && !NH) st_atomic_add(&hist[bin], 1u);
-#endif
-#if ST_DIAG & 2
-                    dck += mix64((((uint64_t)(uint32_t)rm0 << 32) | key_lo) ^ ((uint64_t)base << 48));
-#endif
+                    if (!NH) st_atomic_add(&hist[bin], 1u);
                 }
                 if (mx1) {
                     tk[base + (mx0 ? 1u : 0u)] = ((uint64_t)(uint32_t)rm1 << 32) | (key_lo + 1u);
-#if !(ST_KEYS_LDS && ST_HIST_FLUSH)
                     const uint32_t bin = min(((uint32_t)rm1 - thr_bits) >> 15, (uint32_t)(VO_HIST_BINS - 1));
-                    if (!(ST_PROBE_NOSTORE & 4) && !NH) st_atomic_add(&hist[bin], 1u);
-#endif
-#if ST_DIAG & 2
-                    dck += mix64((((uint64_t)(uint32_t)rm1 << 32) | (key_lo + 1u)) ^ ((uint64_t)(base + (mx0 ? 1u : 0u)) << 48));
-#endif
+                    if (!NH) st_atomic_add(&hist[bin], 1u);
                 }
             }
             toffA += cA; toffB += cB;
@@ -1138,9 +922,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
         // the group's 16 row offsets to SGPRs up front: a v_readlane right before the buffer load
         // whose offset it feeds costs the wave five wait states (s_nop 4) per row
         int soff[ST_TH];
-#if ST_SOFF_HOIST
         st_for([&](auto U) { soff[U] = __builtin_amdgcn_readlane(rows, U); }, std::make_integer_sequence<int, ST_TH>{});
-#endif
         st_for([&](auto U) {
             uint32_t cur = ahead[U % LA];
             if constexpr (BP) {
@@ -1150,75 +932,36 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
             // the row requested here is consumed only if it lies inside the segment: in the last group
             // the requests of steps U >= ST_TH - LA would read past it (wave-uniform; none for SEGT 1)
             if (U < ST_TH - LA || (SEGT > 1 && i + 1 < ntl)) {
-#if ST_SOFF_HOIST
                 ahead[U % LA] = load(soff[U]);
-#else
-                (void)soff;
-                ahead[U % LA] = load(__builtin_amdgcn_readlane(rows, U));
-#endif
             }
             step(P5{}, k0 + U, cur, U);
         }, std::make_integer_sequence<int, ST_TH>{});
         // the 16 row counts of tile A (lanes 0..15) and B (16..31) are contiguous
         const int tileA = (ys / ST_TH + i) * ntx + 2 * sxi;
-        if (lane < (hasB ? 2 * ST_TH : ST_TH) && !(ST_PROBE_NOSTORE & 2)) tilerows[tileA * ST_TH + lane] = (uint8_t)trows;
-#if ST_KEYS_LDS
+        if (lane < (hasB ? 2 * ST_TH : ST_TH)) tilerows[tileA * ST_TH + lane] = (uint8_t)trows;
         {
             // the group's keys: tile A's toffA from slot 0, tile B's toffB from ST_TCAP (tile A + 1's
             // region of cand), copied out in order by consecutive lanes.  LDS operations of one wave
             // complete in order, so the next group's writes cannot overtake these reads.
-            // ST_HIST_FLUSH (and always in the FLAT form): each flushed key's histogram count here
+            // In the FLAT form each flushed key's histogram count is added here
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             uint64_t* __restrict__ dst = cand + (size_t)tileA * ST_TCAP;
-            constexpr bool hf = (FLAT || ST_HIST_FLUSH) && !NH;
+            constexpr bool hf = FLAT && !NH;
             for (int j = lane; j < toffA; j += 64) {
                 const uint64_t kv = wkeys[j];
-                if (!(ST_PROBE_NOSTORE & 2)) dst[j] = kv;
+                dst[j] = kv;
                 if constexpr (hf) st_atomic_add(&hist[min(((uint32_t)(kv >> 32) - thr_bits) >> 15, (uint32_t)(VO_HIST_BINS - 1))], 1u);
             }
             for (int j = lane; j < toffB; j += 64) {
                 const uint64_t kv = wkeys[ST_TCAP + j];
-                if (!(ST_PROBE_NOSTORE & 2)) dst[ST_TCAP + j] = kv;
+                dst[ST_TCAP + j] = kv;
                 if constexpr (hf) st_atomic_add(&hist[min(((uint32_t)(kv >> 32) - thr_bits) >> 15, (uint32_t)(VO_HIST_BINS - 1))], 1u);
             }
         }
-#endif
-#if ST_DIAG & 2
-        // per tile: the sum over its keys of mix64(key ^ slot << 48), lanes 0..31 tile A, 32..63 tile B
-#pragma unroll
-        for (int off = 1; off < 32; off <<= 1) dck += __shfl_xor(dck, off);
-        if (d.tile_ck && (lane == 0 || (lane == 32 && hasB)))
-            d.tile_ck[(size_t)z * d.ntiles + tileA + (lane >> 5)] = dck;
-        dck = 0ull;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            sck += __shfl_xor(sck, off);
-            rck += __shfl_xor(rck, off);
-        }
-        if (d.diag_src && lane == 0 && dfr < VO_DIAG_FRAMES) {
-            d.diag_src[(size_t)dfr * d.ntiles + tileA] = sck;
-            d.diag_resp[(size_t)dfr * d.ntiles + tileA] = rck;
-        }
-        sck = 0ull; rck = 0ull;
-#elif ST_DIAG & 4
-        // per lane group of 16 (lanes 0-15, 16-31: tile A's columns; 32-47, 48-63: tile B's) a word
-        // of the (f, tileA) entry: the checksums of the four quarter-waves
-        {
-            uint32_t q = lsck;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) q = q * 0x9E3779B1u + (uint32_t)__shfl_xor((int)q, off);
-            const uint32_t q0 = __shfl(q, 0), q1 = __shfl(q, 16), q2 = __shfl(q, 32), q3 = __shfl(q, 48);
-            if (d.diag_src && lane == 0 && dfr < VO_DIAG_FRAMES) {
-                d.diag_src[(size_t)dfr * d.ntiles + tileA] = ((unsigned long long)q1 << 32) | q0;
-                if (hasB) d.diag_src[(size_t)dfr * d.ntiles + tileA + 1] = ((unsigned long long)q3 << 32) | q2;
-            }
-        }
-        lsck = 0u;
-#endif
     }
 }
 
-#if ST_NOPK && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
 
@@ -1229,9 +972,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ST_WAV
 // (feature_extraction_parallel_GPU.cpp:259-265).
 // ---------------------------------------------------------------------------
 #define SEL_MAX 4096
-#ifndef SEL_DOT4
-#define SEL_DOT4 1
-#endif
 #define BND_CAP 2048
 #define SEL_MAX_TILES 3072
 #define SEL_LDS_BITS 65536
@@ -1331,19 +1071,6 @@ __global__ void __launch_bounds__(1024) k_select(VoDev d, int f0, int slot_overr
     uint64_t* s_keys = reinterpret_cast<uint64_t*>(smem + L.keys);
     uint32_t* s_lh = reinterpret_cast<uint32_t*>(smem + L.hist);
     const size_t TCAP = ST_TCAP;
-#if LDS_POISON
-    // diagnostic build: the whole dynamic LDS and the static words filled with a launch-varying
-    // pattern first, so a read of LDS this workgroup did not write shows up as a result change
-    {
-        const uint32_t pz = (uint32_t)wall_clock64() * 0x9E3779B9u ^ (uint32_t)blockIdx.x;
-        uint32_t* w = reinterpret_cast<uint32_t*>(smem);
-        for (int i = threadIdx.x; i < d.sel_lds / 4; i += 1024) w[i] = pz + (uint32_t)i * 0x85EBCA6Bu;
-        if (threadIdx.x < 16) { s_hs[threadIdx.x] = pz; s_wsum[threadIdx.x] = (int)pz; }
-        if (threadIdx.x < 256) s_dh[threadIdx.x] = pz;
-        if (threadIdx.x == 0) { s_tb = ((uint64_t)pz << 32) | pz; s_dsel = (int)pz; s_rem = (int)pz; }
-        __syncthreads();
-    }
-#endif
     if (tid == 0) {
         s_nbnd = 0; s_b = -1; s_above = 0;
         s_slot = ext_slot(d, f0, z, slot_override);
@@ -1396,9 +1123,8 @@ __global__ void __launch_bounds__(1024) k_select(VoDev d, int f0, int slot_overr
     uint64_t* keys = staged ? s_keys : d.ckeys + (size_t)z * d.cand_cap;
     // a thread per tile copies the tile's keys to their compact positions (the keys of a tile
     // are contiguous in both; a binary search of the tile per key cost ten dependent LDS reads).
-    // SL_STAGE2: two threads per tile (every other key), eight loads in flight per thread -- a
+    // Two threads per tile (every other key), eight loads in flight per thread -- a
     // KITTI tile's ~14 keys in one round trip, and all 1024 threads busy (528 tiles)
-#if SL_STAGE2 && !ST_DIAG
     for (int t2 = tid; t2 < 2 * ntiles; t2 += 1024) {
         const int t = t2 >> 1, h = t2 & 1;
         const int b = s_tpre[t], n = s_tpre[t + 1] - b;
@@ -1415,70 +1141,10 @@ __global__ void __launch_bounds__(1024) k_select(VoDev d, int f0, int slot_overr
                 }
         }
     }
-    if (false)
-#endif
-    for (int t = tid; t < ntiles; t += 1024) {
-        const int b = s_tpre[t], n = s_tpre[t + 1] - b;
-        const uint64_t* src = cand + (size_t)t * TCAP;
-#if ST_DIAG
-        unsigned long long ck = 0ull;
-        uint32_t prev_lo = 0u;
-        int bad = -1;
-        const int tr = t / ntx, tx = t % ntx;
-#endif
-        for (int i = 0; i < n; i += 4) {
-            uint64_t v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = i + u < n ? src[i + u] : 0ull;
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (i + u < n) {
-                    keys[b + i + u] = v[u];
-                    if (lhist) atomicAdd(&s_lh[sel_bin(v[u], d.thr_bits)], 1u);
-                }
-#if ST_DIAG
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (i + u < n) {
-                    // the slot index: tile A's keys from 0, tile B's from ST_TCAP (k_stencil base)
-                    const uint64_t slot = (uint64_t)(i + u) + ((tx & 1) ? ST_TCAP : 0);
-                    ck += mix64(v[u] ^ (slot << 48));
-                    const uint32_t lo = (uint32_t)v[u], row = lo >> 16, col = lo & 0xFFFF;
-                    const bool ok = (int)row / ST_TH == tr && (int)col / ST_TW == tx && (uint32_t)(v[u] >> 32) > d.thr_bits &&
-                                    (i + u == 0 || lo > prev_lo);
-                    if (!ok && bad < 0) bad = i + u;
-                    prev_lo = lo;
-                }
-#endif
-        }
-#if ST_DIAG
-        if (d.diag_tile && f0 + z < VO_DIAG_FRAMES) d.diag_tile[(size_t)(f0 + z) * ntiles + t] = ck;
-        if ((ST_DIAG & 2) && d.dbg && d.tile_ck) {
-            const unsigned long long want = d.tile_ck[(size_t)z * ntiles + t];
-            atomicAdd(&d.dbg[24000], 1ull);
-            if (want != ck || bad >= 0) {
-                atomicAdd(&d.dbg[want != ck ? 24001 : 24002], 1ull);
-                if (atomicCAS(&d.dbg[24003], 0ull, (unsigned long long)(f0 + z + 1)) == 0ull) {
-                    d.dbg[24004] = (unsigned long long)t;
-                    d.dbg[24005] = want;
-                    d.dbg[24006] = ck;
-                    d.dbg[24007] = (unsigned long long)n;
-                    d.dbg[24008] = (unsigned long long)(bad + 1);
-                    for (int i = 0; i < n && i < 24; ++i) d.dbg[24010 + i] = src[i];
-                }
-            }
-        }
-#endif
-    }
     // tests only (VO_FAULT_INJECT=1): N counts more in the top bin than the tiles hold keys, as
     // k_inject_hist adds to a stencil-built histogram -- the consistency check below must fire
     if (lhist && d.fault_inject && tid == 0) atomicAdd(&s_lh[VO_HIST_BINS - 1], (uint32_t)N);
     __syncthreads();
-#if ST_DIAG
-    if (d.diag_keys && f0 + z < VO_DIAG_FRAMES)
-        for (int g = tid; g < VO_DIAG_KEYS; g += 1024)
-            d.diag_keys[(size_t)(f0 + z) * VO_DIAG_KEYS + g] = g < C ? keys[g] : 0ull;
-#endif
     VO_STAMP(d, 1900 + (int)blockIdx.x, 1);
     // C (the histogram is read for every frame: its total must equal C, the consistency check)
     int b = -1;
@@ -1650,7 +1316,6 @@ __global__ void __launch_bounds__(1024) k_select(VoDev d, int f0, int slot_overr
             const uint4 rc = s_rows[t];
             const uint32_t w4[4] = {rc.x, rc.y, rc.z, rc.w};
             int start = 0;
-#if SEL_DOT4
             // the row counts below r (bytes of the four words): each word masked to its bytes below
             // r (a 64-bit shift covers the whole-word and empty cases) and summed by v_dot4_u32_u8
             // -- no compare / select per row
@@ -1660,11 +1325,6 @@ __global__ void __launch_bounds__(1024) k_select(VoDev d, int f0, int slot_overr
                 const uint32_t m = (uint32_t)(0xFFFFFFFFull >> (32 - sh));
                 start = (int)__builtin_amdgcn_udot4(w4[k] & m, 0x01010101u, (uint32_t)start, false);
             }
-#else
-#pragma unroll
-            for (int q = 0; q < ST_TH; ++q)
-                if (q < r) start += (int)((w4[q >> 2] >> (8 * (q & 3))) & 0xFF);
-#endif
             const int gs = s_tpre[t] + start;
             // selected keys before g inside the segment
             int within = 0;
@@ -2433,23 +2093,10 @@ __global__ void k_ext_missing(VoDev d, int slot)
 // No cross-lane traffic, no barrier.
 // ---------------------------------------------------------------------------
 #define DS_KPW 64
-#ifndef DS_ALIGNBIT
-#define DS_ALIGNBIT 1
-#endif
 #ifndef DS_WAVES
 #define DS_WAVES 4
 #endif
 #define DS_KPB (DS_KPW * DS_WAVES)
-#ifndef DS_PKSUB
-#define DS_PKSUB 0             // 1: the orientation sums' sample differences two per v_pk_add_f32 (12 % fewer orientation VALU, but KITTI 288-290k vs 293-298k, r4s)
-#endif
-#ifndef DS_PROBE
-#define DS_PROBE 0             // diagnostic builds only: 1 hot table, 2 no orientation sums (wrong descriptors)
-#endif
-#ifndef DS_UNROLL
-#define DS_UNROLL 0            // 1: the orientation sums fully unrolled from sample registers (describe
-                               // 0.92 -> 0.85 us/frame but KITTI 278-285k vs 283-289k: 110 VGPRs, 30 KB code)
-#endif
 
 // the FREAK lists of include/vo_freak_tables.h as compile-time tables; pair e is the e-th
 // (p, q), p < q, row-major (ensure_tables enumerates the same order)
@@ -2490,13 +2137,9 @@ __device__ __forceinline__ uint32_t ds_word(const uint32_t (&r)[VO_FREAK_NPOINTS
     st_for([&](auto J) {
         constexpr int t = 32 * W + 31 - decltype(J)::value;          // highest test first
         constexpr int e = kDs.patch[t];
-#if DS_ALIGNBIT
         // (word << 1) | (I(q) - I(p) < 0): v_sub + v_alignbit_b32 (funnel shift of word:diff by 31),
         // no compare, no VCC select and its wait states (samples are bytes: no overflow)
         word = __builtin_amdgcn_alignbit(word, r[kDs.pq[e]] - r[kDs.pp[e]], 31u);
-#else
-        word = (word << 1) | (r[kDs.pp[e]] > r[kDs.pq[e]] ? 1u : 0u);
-#endif
     }, std::make_integer_sequence<int, 32>{});
     return word;
 }
@@ -2518,50 +2161,6 @@ __device__ __forceinline__ void describe_wave(const VoDev& d, const uint8_t* __r
     // and the gathers need no branches (their values are never used)
     const int2 kp = valid ? d.kps[(size_t)cur * d.N + base + lane] : make_int2(d.bcol, d.brow);
     ds_f2 oxy = {0.0f, 0.0f};
-#if DS_UNROLL
-    // 1. the 43 pattern samples, in registers
-    float smp[NP];
-    {
-        uint32_t v[NP];
-        st_for([&](auto U) {
-            constexpr int u = decltype(U)::value;
-            v[u] = img[(size_t)(kp.y + kDs.py[u]) * Wb + (kp.x + kDs.px[u])];
-        }, std::make_integer_sequence<int, NP>{});
-        st_for([&](auto U) { smp[U] = (float)v[U]; }, std::make_integer_sequence<int, NP>{});
-    }
-    (void)s_I0;
-    VO_STAMP(d, stamp_slot, 1);
-    // 2. O = sum over pairs t = 0..902 of (ic * d) / |d|, each component in order in f32, fully
-    //    unrolled: the pair (p, q) of term t is a compile-time constant, so ic = I(p) - I(q) reads
-    //    two sample registers and the sums need no LDS, no padding terms and no loop control.  The
-    //    table arrives by scalar loads, one block of DS_UB entries ahead of the block being summed.
-    {
-        constexpr int NB = (VO_FREAK_NPAIRS + DS_UB - 1) / DS_UB;
-        float4 tb[DS_UB], tbn[DS_UB];
-#pragma unroll
-        for (int u = 0; u < DS_UB; ++u) tb[u] = c_orient_u[u];
-        st_for([&](auto Bk) {
-            constexpr int b = decltype(Bk)::value;
-            // block b's entries (requested during block b - 1) have arrived; request block b + 1
-            __builtin_amdgcn_s_waitcnt(0xC07F);         // lgkmcnt(0)
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (b + 1 < NB) {
-#pragma unroll
-                for (int u = 0; u < DS_UB; ++u) tbn[u] = c_orient_u[(b + 1) * DS_UB + u];
-            }
-            __builtin_amdgcn_sched_barrier(0);          // the requests stay ahead of the sums
-            st_for([&](auto U) {
-                constexpr int t = b * DS_UB + decltype(U)::value;
-                if constexpr (t < VO_FREAK_NPAIRS) orient_term(smp[kDs.pp[t]] - smp[kDs.pq[t]], tb[U], oxy);
-            }, std::make_integer_sequence<int, DS_UB>{});
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (b + 1 < NB) {
-#pragma unroll
-                for (int u = 0; u < DS_UB; ++u) tb[u] = tbn[u];
-            }
-        }, std::make_integer_sequence<int, NB>{});
-    }
-#else
     // 1. the 43 pattern samples -> this lane's LDS column (all loads in flight first)
     {
         uint32_t v[NP];
@@ -2579,11 +2178,7 @@ __device__ __forceinline__ void describe_wave(const VoDev& d, const uint8_t* __r
     //    the zero rows past the samples.  Software-pipelined: the samples and table entries of
     //    group g + 1 are requested before group g is summed.
     {
-#if DS_PROBE == 2
-        constexpr int NG = 1;                           // probe: no orientation sums
-#else
         constexpr int NG = DS_ONPAD / DS_OG;
-#endif
         const float* col = &s_I0[0][lane];
         int p = 0, qs = 1;                              // group g: row p, samples qs .. qs + 7
         float ip = col[0], iq[DS_OG];
@@ -2610,33 +2205,17 @@ __device__ __forceinline__ void describe_wave(const VoDev& d, const uint8_t* __r
             float4 tbn[DS_OG];
 #pragma unroll
             for (int u = 0; u < DS_OG; ++u) {
-#if DS_PROBE == 1
-                iqn[u] = col[(qn + u) * DS_KPW]; tbn[u] = c_orient[(gn & 3) * DS_OG + u];   // probe: a hot 512-byte table
-#else
                 iqn[u] = col[(qn + u) * DS_KPW]; tbn[u] = LT ? s_tab[gn * DS_OG + u] : c_orient[gn * DS_OG + u];
-#endif
             }
             __builtin_amdgcn_sched_barrier(0);          // the requests stay ahead of the sums
 #pragma unroll
-#if DS_PKSUB
-            // two sample differences per packed subtract (exact: integers), each broadcast into
-            // its term's packed product by op_sel
-            for (int u = 0; u < DS_OG; u += 2) {
-                static_assert(DS_OG % 2 == 0, "pairs of terms");
-                const ds_f2 dd = ds_f2{ip, ip} - ds_f2{iq[u], iq[u + 1]};
-                orient_term(dd.x, tb[u], oxy);
-                orient_term(dd.y, tb[u + 1], oxy);
-            }
-#else
             for (int u = 0; u < DS_OG; ++u) orient_term(ip - iq[u], tb[u], oxy);
-#endif
             __builtin_amdgcn_sched_barrier(0);
             p = pn; qs = qn; ip = ipn;
 #pragma unroll
             for (int u = 0; u < DS_OG; ++u) { iq[u] = iqn[u]; tb[u] = tbn[u]; }
         }
     }
-#endif
     VO_STAMP(d, stamp_slot, 2);
     const float ox = oxy.x, oy = oxy.y;
     // 3. angle and rotation
@@ -2681,20 +2260,12 @@ template <bool LT>
 __global__ void __launch_bounds__(64 * DS_WAVES) k_describe(VoDev d, int f0, int slot_override, unsigned publish,
                                                             int nb)
 {
-    __shared__ float s_I0[DS_WAVES][DS_UNROLL ? 1 : DS_OROWS][DS_KPW];   // sample columns (the looped sums)
+    __shared__ float s_I0[DS_WAVES][DS_OROWS][DS_KPW];   // sample columns (the looped sums)
     __shared__ float4 s_tab[LT ? DS_ONPAD : 1];                          // LT: the pair table
     if constexpr (LT) {
         for (int i = threadIdx.x; i < DS_ONPAD; i += 64 * DS_WAVES) s_tab[i] = c_orient[i];
         __syncthreads();
     }
-#if LDS_POISON
-    {
-        const uint32_t pz = (uint32_t)wall_clock64() * 0x9E3779B9u ^ (uint32_t)blockIdx.x;
-        float* w = &s_I0[0][0][0];
-        for (int i = threadIdx.x; i < (int)(sizeof(s_I0) / 4); i += 64 * DS_WAVES) w[i] = __uint_as_float(pz + (uint32_t)i);
-        __syncthreads();
-    }
-#endif
     int z, bx;
     if (xcd_frame(d, (d.N + DS_KPB - 1) / DS_KPB, nb, z, bx)) {
         const int cur = ext_slot(d, f0, z, slot_override);
@@ -2741,9 +2312,6 @@ __host__ __device__ constexpr int dp_pair_q(int t)
 }
 static_assert(dp_pair_p(0) == 0 && dp_pair_q(0) == 1 && dp_pair_p(42) == 1 && dp_pair_q(42) == 2, "pair order");
 #define DP_WAVES 8
-#ifndef DP_CT_TERMS
-#define DP_CT_TERMS 1                  // term waves with compile-time pairs and samples in registers
-#endif
 #define DP_CH DP_CHUNK                               // terms per chunk of the LDS ring (two chunks)
 // k_describe_pf's term wave W (1 .. DP_WAVES - 1): the terms t = W - 1 (mod DP_WAVES - 1) of each
 // chunk, generated at compile time (pairs as register indices into the wave's 43 samples, weights by
@@ -2778,10 +2346,6 @@ __global__ void __launch_bounds__(64 * DP_WAVES) k_describe_pf(VoDev d, int f0, 
     __shared__ float s_I[NP][64];                    // pattern samples (then the rotated samples, as u32)
     __shared__ ds_f2 s_t[2][DP_CH + 1][64];          // orientation terms, a chunk ahead (+ a spare row)
     __shared__ float s_c[64], s_s[64];
-#if !DP_CT_TERMS
-    __shared__ float4 s_orient[DP_NPAD];
-    __shared__ uint32_t s_pairoff[DP_NPAD];
-#endif
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int cur = ext_slot(d, f0, 0, slot_override);
     const int n = d.ext_n[cur];
@@ -2793,13 +2357,6 @@ __global__ void __launch_bounds__(64 * DP_WAVES) k_describe_pf(VoDev d, int f0, 
     VO_STAMP(d, sslot, 0);
     const bool valid = base + lane < n;
     const int2 kp = valid ? d.kps[(size_t)cur * d.N + base + lane] : make_int2(d.bcol, d.brow);
-#if !DP_CT_TERMS
-    // 0. the term tables into LDS
-    for (int t = threadIdx.x; t < DP_NPAD; t += 64 * DP_WAVES) {
-        s_orient[t] = c_orient_pf[t];
-        s_pairoff[t] = c_pairoff[t];
-    }
-#endif
     // 1. pattern samples, rows u = wave, wave + DP_WAVES, ...
     for (int u = wave; u < NP; u += DP_WAVES)
         s_I[u][lane] = (float)img[(size_t)(kp.y + (int)c_ppt[u].y) * Wb + (kp.x + (int)c_ppt[u].x)];
@@ -2813,40 +2370,7 @@ __global__ void __launch_bounds__(64 * DP_WAVES) k_describe_pf(VoDev d, int f0, 
     //    barrier: 47k of the wave's 62k cycles)
     //    The tables come from LDS (copied at entry): scalar loads share lgkmcnt with the LDS
     //    reads, so every term waited for its scalar load's full latency (54k cycles at wave 0)
-#if !DP_CT_TERMS
-    static_assert(DP_CH == DP_CHUNK, "k_describe_pf's chunk is its tables' padding unit");
-    const unsigned char* sIb = reinterpret_cast<const unsigned char*>(&s_I[0][0]) + 4 * lane;
-    auto terms = [&](int c) {
-        constexpr int TPW = (DP_CH + DP_WAVES - 2) / (DP_WAVES - 1);
-        // branch-free (a wave's run past the chunk writes the spare row DP_CH), so the compiler
-        // issues the run's LDS reads together instead of three dependent round trips per term
-        // (in three sweeps -- the run's pair offsets, then its samples and weights, then the terms
-        // -- so each sweep's reads are in flight together)
-        uint32_t po[TPW];
-        float4 tb[TPW];
-        float ia[TPW], ib[TPW];
-#pragma unroll
-        for (int i = 0; i < TPW; ++i) {
-            const int t = c * DP_CH + min(wave - 1 + (DP_WAVES - 1) * i, DP_CH - 1);
-            po[i] = s_pairoff[t];
-            tb[i] = s_orient[t];
-        }
-#pragma unroll
-        for (int i = 0; i < TPW; ++i) {
-            ia[i] = *reinterpret_cast<const float*>(sIb + (po[i] & 0xFFFFu));
-            ib[i] = *reinterpret_cast<const float*>(sIb + (po[i] >> 16));
-        }
-#pragma unroll
-        for (int i = 0; i < TPW; ++i) {
-            const int j = min(wave - 1 + (DP_WAVES - 1) * i, DP_CH);
-            const float ic = ia[i] - ib[i];
-            const ds_f2 i2 = {ic, ic};
-            s_t[c & 1][j][lane] = __builtin_elementwise_fma(i2, ds_f2{tb[i].x, tb[i].y}, i2 * ds_f2{tb[i].z, tb[i].w});
-        }
-    };
-#endif
     ds_f2 oxy = {0.0f, 0.0f};
-#if DP_CT_TERMS
     // term wave W (1 .. DP_WAVES - 1) computes the terms t = W - 1 (mod DP_WAVES - 1) with
     // compile-time pairs: its 43 samples in registers, the weights by scalar loads, no table or
     // sample reads through LDS (those made the term waves LDS-bound: 25-29k cycles per block)
@@ -2874,20 +2398,6 @@ __global__ void __launch_bounds__(64 * DP_WAVES) k_describe_pf(VoDev d, int f0, 
     case 6: dp_term_wave<6>(I, s_t, lane, std::make_integer_sequence<int, NC>{}); break;
     default: dp_term_wave<7>(I, s_t, lane, std::make_integer_sequence<int, NC>{}); break;
     }
-#else
-    if (wave > 0) terms(0);
-    __syncthreads();
-    for (int c = 0; c < NC; ++c) {
-        if (wave > 0) {
-            if (c + 1 < NC) terms(c + 1);
-        } else {
-            const int m = min(DP_CH, VO_FREAK_NPAIRS - c * DP_CH);
-#pragma unroll 16
-            for (int j = 0; j < m; ++j) oxy = oxy + s_t[c & 1][j][lane];
-        }
-        __syncthreads();
-    }
-#endif
     VO_STAMP(d, sslot, 2);
     // 3. angle and rotation (wave 0), as describe_wave
     if (wave == 0) {
@@ -3461,48 +2971,18 @@ __device__ __forceinline__ int dpp_g8(int v, int step)
     default: return __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true);
     }
 }
-// lane q of each 8-lane group -> every lane of the group (ds_swizzle bitmask mode:
-// and_mask 0x18, or_mask q)
-template <int Q>
-__device__ __forceinline__ int g8_bcast(int v)
-{
-    return __builtin_amdgcn_ds_swizzle(v, 0x18 | (Q << 5));
-}
-template <int Q>
-__device__ __forceinline__ double g8_bcast_d(double v)
-{
-    const long long x = __double_as_longlong(v);
-    const int lo = g8_bcast<Q>((int)(x & 0xFFFFFFFFll)), hi = g8_bcast<Q>((int)(x >> 32));
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
 // a[c] for a group-uniform runtime column c (9-way select)
-#ifndef RS_FASTSEL
-#define RS_FASTSEL 1
-#endif
 #define RS_GROUPS_MAX 32       // lane groups of eight per workgroup (k_ransac_hyp<4>: 256 threads)
 __device__ __forceinline__ double sel9(const double (&a)[9], int c)
 {
-#if RS_FASTSEL
     // a[c], c in [0, 8], as a select tree on the bits of c: four masks, each reused
     const bool b0 = (c & 1) != 0, b1 = (c & 2) != 0, b2 = (c & 4) != 0, b3 = (c & 8) != 0;
     const double v01 = b0 ? a[1] : a[0], v23 = b0 ? a[3] : a[2], v45 = b0 ? a[5] : a[4], v67 = b0 ? a[7] : a[6];
     const double v03 = b1 ? v23 : v01, v47 = b1 ? v67 : v45;
     const double v07 = b2 ? v47 : v03;
     return b3 ? a[8] : v07;
-#else
-    double v = a[0];
-#pragma unroll
-    for (int j = 1; j < 9; ++j) v = c == j ? a[j] : v;
-    return v;
-#endif
 }
 
-#ifndef RS_FASTRED
-#define RS_FASTRED 1                   // Gauss-Jordan pivot: group max, then min index among the maxima
-#endif
-#ifndef RS_LDSPIV
-#define RS_LDSPIV 1                    // Gauss-Jordan pivot row through LDS (else lane shuffles)
-#endif
 #define RS_ROWSTRIDE 10                // doubles per lane row in LDS (16-byte aligned rows)
 // computeFundamentalMatrix on a minimal sample (ransac.cpp:63-93) for the lane group's
 // hypothesis: Gauss-Jordan with complete pivoting exactly as oracle nullvec_8x9 (pivot = max
@@ -3548,7 +3028,6 @@ __device__ void fit_F8_group(const double* __restrict__ pts, const int s8[8], in
         // lane-local candidate: first max |a| over the unused columns of an unused row
         double bv = -1.0;
         int bi = 1 << 30;
-#if RS_FASTSEL
         // the same first maximum as a tournament (depth 4 instead of a 9-step compare / select
         // chain): candidates are |a| over unused columns, > 0, else -1; a later one wins only if
         // strictly greater, so ties go to the smaller column
@@ -3572,20 +3051,10 @@ __device__ void fit_F8_group(const double* __restrict__ pts, const int s8[8], in
             win(w0, i0, mv[8], 8);
             if (!((used_r >> r) & 1u) && w0 > 0.0) { bv = w0; bi = r * 16 + i0; }
         }
-#else
-        if (!((used_r >> r) & 1u)) {
-#pragma unroll
-            for (int c = 0; c < 9; ++c) {
-                const double v = fabs(a[c]);
-                if (!((used_c >> c) & 1u) && v > 0.0 && v > bv) { bv = v; bi = r * 16 + c; }
-            }
-        }
-#endif
         // group maximum, ties to the smaller flat index: the maximum value first (three DPP max
         // steps; candidates are positive or -1, never NaN), then the smallest index among the lanes
         // holding it (three DPP min steps) -- the same pivot as the pairwise (value, index) reduction
         // with its compare / select chains
-#if RS_FASTRED
         {
             double gm = bv;
 #pragma unroll
@@ -3599,20 +3068,9 @@ __device__ void fit_F8_group(const double* __restrict__ pts, const int s8[8], in
             bv = gm;
             bi = ci;
         }
-#else
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            const double ov = dpp_f64(bv, t);
-            const int oi = dpp_g8(bi, t);
-            const bool take = ov > bv || (ov == bv && oi < bi);
-            bv = take ? ov : bv;
-            bi = take ? oi : bi;
-        }
-#endif
         live = live && bv > 0.0;                    // rank deficient: remaining columns free
         // (flat index r * 16 + c: the same order as r * 9 + c, row and column by shift and mask)
         const int pr = bi >> 4, pc = bi & 15;
-#if RS_LDSPIV
         // the pivot row, A[r][pc] and the pivot through LDS: each lane stores its row, then reads
         // the group's pivot row and its own entry in column pc (12 LDS instructions instead of 20
         // lane shuffles and a nine-way select).  One wave's lanes only, ordered by wave barriers.
@@ -3640,14 +3098,6 @@ __device__ void fit_F8_group(const double* __restrict__ pts, const int s8[8], in
             arpc = mine[pcc];
             piv = prw[pcc];
         }
-#else
-        const double arpc = sel9(a, live ? pc : 0);   // A[r][pc]
-        const int src = gbase + (live ? pr : 0);
-        const double piv = __shfl(arpc, src);
-        double prow[9];
-#pragma unroll
-        for (int c = 0; c < 9; ++c) prow[c] = __shfl(a[c], src);
-#endif
         if (live) {
             used_r |= 1u << pr; used_c |= 1u << pc;
             if (r == pr) my_pc = pc;
@@ -3667,7 +3117,6 @@ __device__ void fit_F8_group(const double* __restrict__ pts, const int s8[8], in
     // back substitution: x_fc = 1, x_pc = -a[pr][fc] / a[pr][pc] from each pivot row
     const double val = my_pc >= 0 ? -(sel9(a, fc) / sel9(a, my_pc)) : 0.0;
     double f[9];
-#if RS_FASTSEL
     // the group's solution vector through LDS: each pivot row stores its x_pc at column pc, the
     // free column holds 1, the rest 0 -- the same vector as eight broadcast rows selected into
     // nine registers (72 compare / select pairs, each padded for its VCC read), in three LDS
@@ -3689,22 +3138,6 @@ __device__ void fit_F8_group(const double* __restrict__ pts, const int s8[8], in
         for (int j = 0; j < 9; ++j) f[j] = fb[j];
         __builtin_amdgcn_wave_barrier();              // the next hypothesis' fit rewrites fb
     }
-#else
-#pragma unroll
-    for (int j = 0; j < 9; ++j) f[j] = (j == fc) ? 1.0 : 0.0;
-    auto take_row = [&](int cq, double vq) {
-#pragma unroll
-        for (int j = 0; j < 9; ++j) f[j] = cq == j ? vq : f[j];
-    };
-    take_row(g8_bcast<0>(my_pc), g8_bcast_d<0>(val));
-    take_row(g8_bcast<1>(my_pc), g8_bcast_d<1>(val));
-    take_row(g8_bcast<2>(my_pc), g8_bcast_d<2>(val));
-    take_row(g8_bcast<3>(my_pc), g8_bcast_d<3>(val));
-    take_row(g8_bcast<4>(my_pc), g8_bcast_d<4>(val));
-    take_row(g8_bcast<5>(my_pc), g8_bcast_d<5>(val));
-    take_row(g8_bcast<6>(my_pc), g8_bcast_d<6>(val));
-    take_row(g8_bcast<7>(my_pc), g8_bcast_d<7>(val));
-#endif
     double nn = 0.0;
 #pragma unroll
     for (int j = 0; j < 9; ++j) nn = nn + f[j] * f[j];
@@ -3723,17 +3156,8 @@ __device__ void fit_F8_group(const double* __restrict__ pts, const int s8[8], in
 #ifndef RS_HYP_J
 #define RS_HYP_J 4                     // Sampson chains in flight per lane
 #endif
-#ifndef RS_HYP_PF
-#define RS_HYP_PF 0                    // the next word's points loaded before this word's tests
-#endif
-#ifndef RS_EARLY
-#define RS_EARLY 1                     // later chunks: a wave's count stops once it cannot pass the best
-#endif
 #ifndef RS_FUSED_J
 #define RS_FUSED_J 8
-#endif
-#ifndef RS_FUSED_PF
-#define RS_FUSED_PF 1
 #endif
 // The word's eight Sampson tests as one branch-free stream (each step over j = 0..7, so eight
 // independent f64 chains are in flight), the threshold form hoisted out of the loop, and the next
@@ -3875,9 +3299,6 @@ __device__ __forceinline__ int count_wave(const double* __restrict__ pts, int sc
 // float4s (j = 4 q .. 4 q + 3), so a packed pair is a register pair as loaded.  The word's bits, the
 // mask store and the early stop are count_words'.
 typedef float vo_f2 __attribute__((ext_vector_type(2)));
-#ifndef RS_S32
-#define RS_S32 1                       // 0: the f64 count for every match (the certificate off)
-#endif
 __device__ __forceinline__ int count_words32(const double* __restrict__ pts, const float* __restrict__ pts32, int scored,
                                              const double* F, const float* cmax, int h, int r, bool store,
                                              uint64_t* __restrict__ mask, int bound, int w0, int ws)
@@ -3913,7 +3334,7 @@ __device__ __forceinline__ int count_words32(const double* __restrict__ pts, con
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const bool valid = w * 64 + j * 8 + r < scored;
-            if (!s.ok || !RS_S32) dec[j] = -1;
+            if (!s.ok) dec[j] = -1;
             und |= valid && dec[j] < 0;
         }
         if (ballot64(und) != 0ull) {                   // wave-uniform: the f64 test where f32 cannot decide
@@ -3966,7 +3387,7 @@ __device__ __forceinline__ int count_wave32(const double* __restrict__ pts, cons
             const float* q = pts32 + (size_t)min(w0 + u, nw - 1) * 256 + lo;
             float diff, bnd, den;
             vo_s32_eval(s, q[0], q[64], q[128], q[192], fma1, abs1, &diff, &bnd, &den);
-            dec[u] = (s.ok && RS_S32) ? vo_s32_decide(diff, bnd, den) : -1;
+            dec[u] = s.ok ? vo_s32_decide(diff, bnd, den) : -1;
         }
         bool und = false;
 #pragma unroll
@@ -4121,6 +3542,7 @@ __device__ void inv4(const double* M, double* Inv)
 // replay publishes w->ready1 when it is done (k0 == 0), or the chunk waits for it first (k0 > 0).
 // W1: one hypothesis per wave (the latency form: every lane group fits the same hypothesis, the
 // wave's 64 lanes split its count) instead of eight
+// CPF: the next word's points loaded before this word's tests (the fused form; off in k_ransac_hyp)
 template <int HPB, int CJ, bool CPF, bool W1 = false>
 __device__ __forceinline__ void ransac_chunk(const VoDev& d, int k0, int k1, int nhyp, int stage, int reps, int bx,
                                              int nbx, bool ready)
@@ -4174,7 +3596,7 @@ __device__ __forceinline__ void ransac_chunk(const VoDev& d, int k0, int k1, int
         kbound = min(w->maxit, k1);
     // counts past the previous replay's best only matter to the loop: a later chunk stops a wave's
     // count once none of its hypotheses can pass it (not the stage API, which returns every count)
-    const int cbound = (RS_EARLY && k0 > 0 && !stage) ? w->best : -1;
+    const int cbound = (k0 > 0 && !stage) ? w->best : -1;
     for (int rep = 0; rep < reps; ++rep, k += nbx * HPB * HPW) {
         const int kb = W1 ? k : k - h;             // the wave's first hypothesis
         if (kb >= k1) break;                       // wave-uniform
@@ -4194,25 +3616,7 @@ __device__ __forceinline__ void ransac_chunk(const VoDev& d, int k0, int k1, int
             VO_STAMP(d, k, 1);
             double F[9];
             fit_F8_group(pts, s8, r, lane & ~7, F, &d, k);
-#if RS_PROBE == 1
-            {   // timing probe: the fit twice (the second result only kept alive)
-                double F2[9];
-                fit_F8_group(pts, s8, r, lane & ~7, F2);
-#pragma unroll
-                for (int j = 0; j < 9; ++j) asm volatile("" ::"v"(F2[j]));
-            }
-#endif
             VO_STAMP(d, k, 2);
-#if RS_PROBE == 2
-            {   // timing probe: rank 2 twice
-                double F2[9];
-#pragma unroll
-                for (int j = 0; j < 9; ++j) { F2[j] = F[j]; asm volatile("" : "+v"(F2[j])); }
-                rank2(F2);
-#pragma unroll
-                for (int j = 0; j < 9; ++j) asm volatile("" ::"v"(F2[j]));
-            }
-#endif
             rank2(F);
             VO_STAMP(d, k, 5);
             if (mine && (!W1 || h == 0)) {
@@ -4277,30 +3681,19 @@ __device__ __forceinline__ void ransac_chunk(const VoDev& d, int k0, int k1, int
     }
 }
 
-#ifndef RS_PROBE
-#define RS_PROBE 0                     // timing probes (variant builds only): 1 the fit twice, 2 rank 2 twice
-#endif
-#ifndef RS_WAVES_EU
-#define RS_WAVES_EU 0                  // 0: the compiler's register budget
-#endif
-#if RS_WAVES_EU
-#define RS_OCC __attribute__((amdgpu_waves_per_eu(RS_WAVES_EU)))
-#else
-#define RS_OCC
-#endif
 template <int HPB>
-__global__ void __launch_bounds__(64 * HPB) RS_OCC k_ransac_hyp(VoDev d, int k0, int k1, int nhyp, int stage, int reps)
+__global__ void __launch_bounds__(64 * HPB) k_ransac_hyp(VoDev d, int k0, int k1, int nhyp, int stage, int reps)
 {
-    ransac_chunk<HPB, RS_HYP_J, RS_HYP_PF>(d, k0, k1, nhyp, stage, reps, blockIdx.x, gridDim.x, false);
+    ransac_chunk<HPB, RS_HYP_J, false>(d, k0, k1, nhyp, stage, reps, blockIdx.x, gridDim.x, false);
 }
 // one frame's two chunks in one launch (the per-frame call and the stage API: one launch and one
 // dependent-launch gap less): workgroups [0, b0) run [0, c0) and publish its replay; the rest wait
 // for it and run [c0, nhyp) as the second launch would
 template <int HPB, bool W1>
-__global__ void __launch_bounds__(64 * HPB) RS_OCC k_ransac_fused(VoDev d, int c0, int nhyp, int stage, int b0, int reps1)
+__global__ void __launch_bounds__(64 * HPB) k_ransac_fused(VoDev d, int c0, int nhyp, int stage, int b0, int reps1)
 {
-    if ((int)blockIdx.x < b0) ransac_chunk<HPB, RS_FUSED_J, RS_FUSED_PF, W1>(d, 0, c0, nhyp, stage, 1, blockIdx.x, b0, true);
-    else ransac_chunk<HPB, RS_FUSED_J, RS_FUSED_PF, W1>(d, c0, nhyp, nhyp, stage, reps1, blockIdx.x - b0, gridDim.x - b0, true);
+    if ((int)blockIdx.x < b0) ransac_chunk<HPB, RS_FUSED_J, true, W1>(d, 0, c0, nhyp, stage, 1, blockIdx.x, b0, true);
+    else ransac_chunk<HPB, RS_FUSED_J, true, W1>(d, c0, nhyp, nhyp, stage, reps1, blockIdx.x - b0, gridDim.x - b0, true);
 }
 
 // ---------------------------------------------------------------------------
@@ -5448,44 +4841,79 @@ __global__ void k_inject_hist(VoDev d, int nb)
 {
     if (threadIdx.x == 0 && (int)blockIdx.x < nb) d.hist[(size_t)blockIdx.x * VO_HIST_BINS + VO_HIST_BINS - 1] += (uint32_t)d.N;
 }
+// the process-scope knobs, read at the first call
+static VoProcEnv read_proc_env()
+{
+    VoProcEnv e = {};
+    e.st_flat = vo_env_flag("VO_ST_FLAT", ST_FLAT_DEFAULT != 0);
+    e.sel_small = vo_env_int("VO_SEL_SMALL", 16);
+    e.stseg = vo_env_int("VO_STSEG", ST_SEGT_DEFAULT);
+    const int pf_segt = vo_env_int("VO_PF_SEGT", 1);
+    e.pf_segt = pf_segt == 2 || pf_segt == 4 ? pf_segt : 1;
+    e.stseg_adapt = vo_env_flag("VO_STSEG_ADAPT", true);
+    e.sel_lds_kb = vo_env_int("VO_SEL_LDS_KB", 158, 40, 158);
+    e.ds_lds_table = vo_env_flag("VO_DS_LDS_TABLE", false);
+    e.ds_pf = vo_env_flag("VO_DS_PF", true);
+    e.ransac_wave_hyp = vo_env_flag("VO_RANSAC_WAVE_HYP", true);
+    // a list, ascending, e.g. "400,700"; "0" or a cut >= max_hyp merges every later chunk into one
+    const char* cuts = getenv("VO_HYP_CUTS");
+    if (!cuts) e.hyp_cuts[e.n_hyp_cuts++] = VO_HYP_CHUNK1;
+    for (const char* q = cuts; q && *q;) {
+        const int x = atoi(q);
+        const int last = e.n_hyp_cuts ? e.hyp_cuts[e.n_hyp_cuts - 1] : VO_HYP_CHUNK0;
+        if (x > last && e.n_hyp_cuts < (int)(sizeof(e.hyp_cuts) / sizeof(e.hyp_cuts[0]))) e.hyp_cuts[e.n_hyp_cuts++] = x;
+        while (*q >= '0' && *q <= '9') ++q;
+        if (*q) ++q;                          // any one separator (',' or ':')
+    }
+    e.rreps = vo_env_int("VO_RREPS", VO_HYP_REPS, 1);
+    e.tri_bpf = vo_env_int("VO_TRI_BPF", TRI_BPF_DEFAULT);
+    e.ransac_split = vo_env_flag("VO_RANSAC_SPLIT", true);
+    e.tail = vo_env_flag("VO_TAIL", true);
+    e.pipe_first = vo_env_flag("VO_PIPE_FIRST", true);
+    e.pf_zerocopy = vo_env_flag("VO_PF_ZEROCOPY", true);
+    e.pf_pinned_direct = vo_env_flag("VO_PF_PINNED_DIRECT", true);
+    e.pf_out_zc = vo_env_flag("VO_PF_OUT_ZC", true);
+    e.plan_dump = vo_env_flag("VO_PLAN_DUMP", false);
+    return e;
+}
+const VoProcEnv& proc_env()
+{
+    static const VoProcEnv e = read_proc_env();
+    return e;
+}
 // the FLAT stencil form (VO_ST_FLAT=1, NMS margins of 5+)
 static bool stencil_flat(const VoDev& d)
 {
-    static const int flat_env = getenv("VO_ST_FLAT") ? atoi(getenv("VO_ST_FLAT")) : ST_FLAT_DEFAULT;
-    return flat_env && d.brow >= 5 && d.bcol >= 5;
+    return proc_env().st_flat && d.brow >= 5 && d.bcol >= 5;
 }
 // k_select builds the batch's histogram in LDS (the stencil writes none): not with the FLAT stencil,
 // nor when the LDS request leaves no room for it
 static bool select_lhist(const VoDev& d)
 {
     const int ntiles = ((d.W + ST_TW - 1) / ST_TW) * ((d.H + ST_TH - 1) / ST_TH);
-    return ST_LHIST && !stencil_flat(d) && sel_layout(ntiles, d.sel_lds).hist >= 0;
+    return !stencil_flat(d) && sel_layout(ntiles, d.sel_lds).hist >= 0;
 }
-// the batch's select is the one-workgroup k_select (launch_select's choice, shared so the two agree)
+// the batch's select is the one-workgroup k_select (launch_stencil and launch_select both ask here)
 static bool select_single_wg(const VoDev& d, int nb)
 {
-    static const int sel_small = getenv("VO_SEL_SMALL") ? atoi(getenv("VO_SEL_SMALL")) : 16;
-    if (d.sel1 && d.sel_emit_lds >= 0 && nb <= sel_small && !d.single) return false;
+    if (d.sel1 && d.sel_emit_lds >= 0 && nb <= proc_env().sel_small && !d.single) return false;
     return d.sel1 && !(d.single && d.sel_emit_lds >= 0);
 }
 void launch_stencil(const VoDev& d, const uint8_t* img0, size_t frame_bytes, int nb, int write_response, hipStream_t s)
 {
     ensure_tables();
     const int ntx = (d.W + ST_TW - 1) / ST_TW, nsx = (ntx + 1) / 2, nty = (d.H + ST_TH - 1) / ST_TH;
-    static const int segt = getenv("VO_STSEG") ? atoi(getenv("VO_STSEG")) : ST_SEGT_DEFAULT;
+    const int segt = proc_env().stseg;
     // one frame (the per-frame call): segments of one tile row, so the frame's waves (4x 8-tile
     // segments' count) each walk 30 source rows instead of 142 -- the latency of the launch
     // the per-frame call's segment (VO_PF_SEGT: 1 or 2 tile rows; 2 reads 1.44x the frame's rows over
     // PCIe instead of 1.88x, in half as many waves of 46 source rows)
-    static const int pf_segt = getenv("VO_PF_SEGT") && (atoi(getenv("VO_PF_SEGT")) == 2 || atoi(getenv("VO_PF_SEGT")) == 4)
-                                   ? atoi(getenv("VO_PF_SEGT")) : 1;
-    int st = write_response ? 4 : nb == 1 && d.single ? pf_segt
+    int st = write_response ? 4 : nb == 1 && d.single ? proc_env().pf_segt
            : segt == 4 || segt == 5 || segt == 6 || segt == 8 ? segt : ST_SEGT_DEFAULT;
     // a small batch (a sequence's ragged last batch): shorter segments until the launch has two
     // waves per SIMD, since its latency is one wave's walk down its segment (8 frames at 6-tile
     // segments: 352 waves of 110 rows, 89 us; at one-tile segments 2112 waves of 30 rows)
-    static const bool seg_adapt = !(getenv("VO_STSEG_ADAPT") && atoi(getenv("VO_STSEG_ADAPT")) == 0);
-    if (seg_adapt && !write_response && st > 1) {
+    if (proc_env().stseg_adapt && !write_response && st > 1) {
         const int steps[4] = {6, 5, 4, 1};
         for (int i = 0; i < 4 && (size_t)nb * nsx * ((nty + st - 1) / st) < 2048; ++i)
             if (steps[i] < st) st = steps[i];
@@ -5497,7 +4925,7 @@ void launch_stencil(const VoDev& d, const uint8_t* img0, size_t frame_bytes, int
     dim3 g(xcd_grid((waves + 3) / 4, nb));
 #define ST_LAUNCH(S, F) hipLaunchKernelGGL((k_stencil<S, false, F>), g, dim3(256), 0, s, d, img0, frame_bytes, 0, nb)
 #define ST_LAUNCH_NH(S) hipLaunchKernelGGL((k_stencil<S, false, false, true>), g, dim3(256), 0, s, d, img0, frame_bytes, 0, nb)
-    // no histogram where k_select builds its own (ST_LHIST=0: the stencil's, as before round 6)
+    // no histogram where k_select builds its own
     const bool nh = !write_response && select_lhist(d) && select_single_wg(d, nb);
     if (write_response)
         hipLaunchKernelGGL((k_stencil<4, true, false>), g, dim3(256), 0, s, d, img0, frame_bytes, write_response, nb);
@@ -5540,15 +4968,7 @@ void launch_select(const VoDev& d, int f0, int nb, int slot_override, hipStream_
     // under the pose queue's kernels it waits for a CU to drain (8 frames: 118 us against 25 us
     // for 64 frames alone, gpurun_out r5j), while the banded kernels' 256-thread workgroups
     // co-run.  (Whole batches keep the one-workgroup form: KITTI within noise either way.)
-    static const int sel_small = getenv("VO_SEL_SMALL") ? atoi(getenv("VO_SEL_SMALL")) : 16;
-    if (d.sel1 && d.sel_emit_lds >= 0 && nb <= sel_small && !d.single) {
-        const dim3 g(xcd_grid(VO_SEL_BANDS, nb));
-        const int cnt_lds = sel_band_layout((d.W + ST_TW - 1) / ST_TW, (d.H + ST_TH - 1) / ST_TH).bits;
-        hipLaunchKernelGGL(k_select_count, g, dim3(SL_T), (size_t)cnt_lds, s, d, f0, slot_override, nb);
-        hipLaunchKernelGGL(k_select_emit, g, dim3(SL_T), (size_t)d.sel_emit_lds, s, d, f0, slot_override, nb);
-        return;
-    }
-    if (d.sel1 && !(d.single && d.sel_emit_lds >= 0)) {
+    if (select_single_wg(d, nb)) {
         // the stencil of this batch wrote no histogram (launch_stencil's nh, the same condition)
         const int lhist = select_lhist(d) ? 1 : 0;
         hipLaunchKernelGGL(k_select, dim3(nb), dim3(1024), (size_t)d.sel_lds, s, d, f0, slot_override, lhist);
@@ -5620,7 +5040,7 @@ int select_lds_bytes(int W, int H, int* key_cap)
     // the whole CU's LDS: keys staged in LDS are read 4 times (a 64 KB request, which lets other
     // kernels share the CU, measured 2-3 % slower end to end)
     // VO_SEL_LDS_KB: a smaller request (the keys then stay in global scratch past its capacity)
-    static const int kb = getenv("VO_SEL_LDS_KB") ? std::max(40, std::min(158, atoi(getenv("VO_SEL_LDS_KB")))) : 158;
+    const int kb = proc_env().sel_lds_kb;
     const int bytes = kb == 158 ? 160 * 1024 - 2048 : kb * 1024;   // static __shared__ of k_select < 2 KB
     if (hipFuncSetAttribute((const void*)k_select, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
         return -1;
@@ -5634,13 +5054,11 @@ void launch_describe(const VoDev& d, int f0, int nb, int slot_override, unsigned
     ensure_tables();
     // VO_DS_LDS_TABLE=1: the per-frame call's describe reads the pair table from LDS (measured: describe
     // 26 -> 30 us, the call 165 -> 168 us, so the scalar-cache path stays the default)
-    static const int lt_env = getenv("VO_DS_LDS_TABLE") ? atoi(getenv("VO_DS_LDS_TABLE")) : 0;
     // (the batched describe with the LDS table, measured round 6: KITTI 280.6-281.5k vs 297.7-302.5k,
     // describe 0.96 -> 1.11 us/frame, r6t)
-    const bool lt = lt_env != 0 && nb == 1 && d.single;
+    const bool lt = proc_env().ds_lds_table && nb == 1 && d.single;
     // the per-frame call: eight waves per 64 keypoints (VO_DS_PF=0: one, k_describe)
-    static const int pf_env = getenv("VO_DS_PF") ? atoi(getenv("VO_DS_PF")) : 1;
-    if (pf_env && nb == 1 && d.single && !publish && !lt) {
+    if (proc_env().ds_pf && nb == 1 && d.single && !publish && !lt) {
         hipLaunchKernelGGL(k_describe_pf, dim3((d.N + 63) / 64), dim3(64 * DP_WAVES), 0, s, d, f0, slot_override);
         return;
     }
@@ -5700,42 +5118,29 @@ void launch_ransac(const VoDev& d, int stage, hipStream_t s, int part)
         // latency is 7 Sampson tests per lane instead of 52 (VO_RANSAC_WAVE_HYP=0: eight hypotheses per
         // wave, 32 per workgroup).  (Round 5 also measured four waves splitting one eight-hypothesis
         // set's count through LDS: slower, 138-140 vs 136.7 us per call.)
-        static const bool w1 = !(getenv("VO_RANSAC_WAVE_HYP") && atoi(getenv("VO_RANSAC_WAVE_HYP")) == 0);
+        const bool w1 = proc_env().ransac_wave_hyp;
         const int hpg = w1 ? 4 : 32;
         const int b0 = (VO_HYP_CHUNK0 + hpg - 1) / hpg, b1 = (nhyp - VO_HYP_CHUNK0 + hpg - 1) / hpg;
         // the later chunk on at most 60 workgroups (hypothesis blocks strided by the grid): its
         // workgroups wait for the first chunk's replay, and hundreds of pollers slowed it
-        static const int wg1 = getenv("VO_RANSAC_WG1") ? std::max(1, atoi(getenv("VO_RANSAC_WG1"))) : 60;
-        const int n1 = std::min(b1, wg1), reps1 = (b1 + n1 - 1) / n1;
+        const int n1 = std::min(b1, 60), reps1 = (b1 + n1 - 1) / n1;
         if (w1) hipLaunchKernelGGL((k_ransac_fused<4, true>), dim3(b0 + n1, nb), dim3(256), 0, s, d, VO_HYP_CHUNK0, nhyp, stage, b0, reps1);
         else hipLaunchKernelGGL((k_ransac_fused<4, false>), dim3(b0 + n1, nb), dim3(256), 0, s, d, VO_HYP_CHUNK0, nhyp, stage, b0, reps1);
         return;
     }
-    // the cuts after [0, VO_HYP_CHUNK0): VO_HYP_CHUNK1 (VO_HYP_CUTS: a list, ascending, e.g. "400,700"; "0"
-    // or a cut >= max_hyp merges every later chunk into one)
-    static const std::vector<int> cuts_env = [] {
-        std::vector<int> v;
-        const char* e = getenv("VO_HYP_CUTS");
-        if (!e) { v.push_back(VO_HYP_CHUNK1); return v; }
-        for (const char* q = e; *q;) {
-            const int x = atoi(q);
-            if (x > VO_HYP_CHUNK0 && (v.empty() || x > v.back())) v.push_back(x);
-            while (*q >= '0' && *q <= '9') ++q;
-            if (*q) ++q;                          // any one separator (',' or ':')
-        }
-        return v;
-    }();
+    // the cuts after [0, VO_HYP_CHUNK0): VO_HYP_CHUNK1, or the environment's list (read_proc_env)
+    const VoProcEnv& pe = proc_env();
     int cut[16], nc = 0;
     cut[nc++] = std::min(nhyp, VO_HYP_CHUNK0);
-    for (int x : cuts_env)
-        if (x < nhyp && nc < 15) cut[nc++] = x;
+    for (int i = 0; i < pe.n_hyp_cuts; ++i)
+        if (pe.hyp_cuts[i] < nhyp) cut[nc++] = pe.hyp_cuts[i];
     cut[nc++] = nhyp;
     int k0 = 0;
     for (int c = 0; c < nc; ++c) {
         const int k1 = cut[c];
         if (k1 <= k0) continue;
         if ((part == 1 && c > 0) || (part == 2 && c == 0)) { k0 = k1; continue; }
-        static const int r2 = getenv("VO_RREPS") ? std::max(1, atoi(getenv("VO_RREPS"))) : VO_HYP_REPS;
+        const int r2 = pe.rreps;
         const int reps = c == 0 ? 1 : (c < nc - 1 ? std::max(1, r2 / 2) : r2);
         const int blocks = ((k1 - k0 + 31) / 32 + reps - 1) / reps;      // 32 hypotheses per workgroup
         hipLaunchKernelGGL((k_ransac_hyp<4>), dim3(blocks, nb), dim3(256), 0, s, d, k0, k1, nhyp, stage, reps);
@@ -5749,7 +5154,7 @@ void launch_refit(const VoDev& d, int with_pose, int stage, hipStream_t s)
 void launch_triangulate(const VoDev& d, int stage, hipStream_t s, VoFrameOut* out, int out_base, int fin)
 {
     // blocks per frame (VO_TRI_BPF; 0 = one (point, candidate) per thread, 4N / TRI_BLOCK blocks)
-    static const int bpf_env = getenv("VO_TRI_BPF") ? atoi(getenv("VO_TRI_BPF")) : TRI_BPF_DEFAULT;
+    const int bpf_env = proc_env().tri_bpf;
     const int full = (4 * d.N + TRI_BLOCK - 1) / TRI_BLOCK;
     const int bpf = bpf_env > 0 ? std::min(bpf_env, full) : full;
     const dim3 g(bpf, stage ? 1 : d.gridw);

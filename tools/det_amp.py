@@ -1,7 +1,7 @@
 """Determinism amplifier: the batched extract of the bench's 1600 KITTI frames, repeated on one
 context and compared frame by frame with its first run, while a second context runs the full path
 (matcher included) on the same frames in a host thread, back to back -- so every extract repeat
-co-runs with pose passes.  The matcher form is the process's (VO_MATCH_MFMA).
+co-runs with pose passes.
 
   python tools/det_amp.py [extract_repeats] [background: full|none]
 """

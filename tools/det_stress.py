@@ -83,42 +83,6 @@ def step(timing):
 modes = [0, 100, 1, 0, 104, 103, 0, 1, 105, 0, 100, 1]
 if os.environ.get("DET_MODES"):
     modes = [int(m) for m in os.environ["DET_MODES"].split(",")]
-dbg = os.environ.get("DET_DBG") == "1"       # MM_VERIFY builds: MFMA key / hand-off counters in d.dbg
-if dbg:
-    import ctypes as C
-    L = ctx.lib
-    L.vo_debug_stamps.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    dbuf = np.zeros(22000, np.uint64)
-
-    def counters():
-        L.vo_debug_stamps(ctx.h, dbuf.ctypes.data_as(C.c_void_p), dbuf.size)
-        return dbuf[6000:6008].astype(np.int64).copy()
-    c_prev = counters()
-diag = os.environ.get("DET_DIAG") == "1"     # ST_DIAG builds: stencil -> select per-tile key checksums
-if diag:
-    import ctypes as C
-    ctx.lib.vo_debug_stamps.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    dgbuf = np.zeros(24040, np.uint64)
-
-    def diag_read():
-        ctx.lib.vo_debug_stamps(ctx.h, dgbuf.ctypes.data_as(C.c_void_p), dgbuf.size)
-        return dgbuf[24000:24040].copy()
-    dg_prev = None
-    diag_frames, diag_tiles = 0, []
-    ctx.lib.vo_debug_diag.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    NFd = S * F
-
-    def diag_arr(what, f0=0, n=NFd):
-        per = ctx.lib.vo_debug_diag(ctx.h, what, 0, 0, None)
-        out = np.zeros((n, per), np.uint64)
-        assert ctx.lib.vo_debug_diag(ctx.h, what, f0, n, out.ctypes.data_as(C.c_void_p)) == per
-        return out
-    NTX = (W + 56) // 57
-
-    def key_str(k):
-        k = int(k)
-        r = np.array([k >> 32], np.uint32).view(np.float32)[0]
-        return f"(x {k & 0xFFFF}, y {(k >> 16) & 0xFFFF}, R {r:.7g})"
 ring = os.environ.get("DET_RING") == "1"     # compare the extracted ring slots too (vo_debug_ring)
 if ring:
     import ctypes as C
@@ -134,13 +98,7 @@ if ring:
         assert rc == 0, rc
         return nk, kp, pr
 ref = step(0)
-if diag:
-    dref = [diag_arr(w) for w in (0, 1, 2)]
-    kref = diag_arr(3)
 ring_ref = ring_read() if ring else None
-if dbg:
-    counters()
-    sel_ref = dbuf[8000:21600].copy()
 bad = 0
 t0 = time.time()
 for r in range(reps):
@@ -148,48 +106,12 @@ for r in range(reps):
     p, st, info = step(m)
     same = np.array_equal(p, ref[0]) and np.array_equal(st, ref[1]) and np.array_equal(info, ref[2])
     msg = ""
-    if dbg:
-        c_now = counters()
-        dc = c_now - c_prev
-        c_prev = c_now
-        msg = (f" mfma keys wrong {dc[0]} of {dc[1]}, stale match_j {dc[2]} of {dc[3]},"
-               f" select: hist total != keys {dc[4]}, need > boundary keys {dc[5]} of {dc[6]} frames")
-    if diag:
-        dg = diag_read()
-        if dg_prev is None or not np.array_equal(dg[1:], dg_prev[1:]):
-            msg += (f" diag: tiles {int(dg[0])} checksum mismatches {int(dg[1])} invalid keys {int(dg[2])}"
-                    + (f"; first: frame {int(dg[3]) - 1} tile {int(dg[4])} stencil ck {int(dg[5]):#x} select ck"
-                       f" {int(dg[6]):#x} n {int(dg[7])} bad index {int(dg[8]) - 1} keys"
-                       f" {[hex(int(k)) for k in dg[10:10 + min(int(dg[7]), 24)]]}" if dg[3] else ""))
-        dg_prev = dg
-        dnow = [diag_arr(w) for w in (0, 1, 2)]
-        names = ("select key ck", "stencil source ck", "stencil response ck")
-        fr_d = sorted(set(int(f) for w in range(3) for f in np.nonzero((dnow[w] != dref[w]).any(1))[0]))
-        diag_frames += len(fr_d)
-        diag_tiles.extend(int(t) for f in fr_d for t in np.nonzero(dnow[0][f] != dref[0][f])[0])
-        for f in fr_d[:3]:
-            msg += f"\n    diag frame {f}:"
-            for w in range(3):
-                t = np.nonzero(dnow[w][f] != dref[w][f])[0]
-                msg += f" {names[w]} tiles {[(int(x), divmod(int(x), NTX)) for x in t[:4]]}"
-            kn = diag_arr(3, f, 1)[0]
-            a, b = set(kref[f][kref[f] != 0].tolist()), set(kn[kn != 0].tolist())
-            ts = np.nonzero(dnow[1][f] != dref[1][f])[0]
-            for t in ts[:4]:
-                msg += f"\n      source ck tile {int(t)}: ref {int(dref[1][f][t]):#018x} now {int(dnow[1][f][t]):#018x}"
-            msg += (f"\n      keys only in ref: {[key_str(k) for k in sorted(a - b)[:6]]}"
-                    f"\n      keys only now:   {[key_str(k) for k in sorted(b - a)[:6]]}")
     if ring:
         nk, kp, pr = ring_read()
         fd = [f for f in range(NF) if nk[f] != ring_ref[0][f] or not np.array_equal(kp[f, :nk[f]], ring_ref[1][f, :nk[f]])
               or not np.array_equal(pr[f, :nk[f]], ring_ref[2][f, :nk[f]])]
         msg += f" ring frames differing: {len(fd)}" + (f" {fd[:6]}" if fd else "")
         for f in fd[:2]:
-            if dbg:
-                sel = dbuf[8000:21600]
-                msg += (f"\n    select frame {f}: key-list checksum {'same' if sel[f] == sel_ref[f] else 'DIFFERS'},"
-                        f" C {sel_ref[4000 + f]} -> {sel[4000 + f]}, Tb {hex(int(sel_ref[8000 + f]))} -> {hex(int(sel[8000 + f]))},"
-                        f" b {sel_ref[12000 + f]} -> {sel[12000 + f]}")
             n0 = ring_ref[0][f]
             kd = np.nonzero((kp[f, :n0] != ring_ref[1][f, :n0]).any(1))[0]
             pd = np.nonzero(pr[f, :n0] != ring_ref[2][f, :n0])[0]
@@ -214,10 +136,6 @@ for r in range(reps):
                   f" | now st {st[s * F + g]} info {info[s * F + g].tolist()}"
                   f" | pose diff {np.abs(p[s * F + g] - ref[0][s * F + g]).max():.3g}")
 print(f"full path: {bad} of {reps} repeats differ", flush=True)
-if diag:
-    odd = sum(1 for t in diag_tiles if (t % NTX) % 2 == 1)
-    print(f"diag: {diag_frames} frame computations differ over the repeats; tiles {len(diag_tiles)}, "
-          f"of them in odd tile columns (lanes 32-63) {odd}", flush=True)
 
 nk0, k0, d0 = ctx.extract_frames_device(dall, outputs=True)
 xbad = 0

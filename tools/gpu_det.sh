@@ -6,7 +6,7 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
-TAG=${1:-det}; REPS=${2:-100}; RUNS=${3:-"libvo_mi355x.so:VO_MATCH_MFMA=1"}; XREPS=${4:-0}
+TAG=${1:-det}; REPS=${2:-100}; RUNS=${3:-"libvo_mi355x.so"}; XREPS=${4:-0}
 O=gpurun_out/$TAG; mkdir -p $O
 if [ -x acs_visual_odometry_amd/bin/buffer_range_probe ]; then
   timeout -k 10 60 acs_visual_odometry_amd/bin/buffer_range_probe > $O/buffer_range_probe.txt || { echo PROBE_FAIL; exit 1; }
@@ -18,6 +18,6 @@ for run in $RUNS; do
   n=$((n + 1))
   echo "== $lib $envs ($REPS repeats)"
   env $envs VO_LIB_PATH=$PWD/acs_visual_odometry_amd/$lib DET_RING=1 timeout -k 10 600 python -u tools/det_stress.py $REPS $XREPS > $O/det_$n.txt 2>&1 || { echo DET_FAIL; tail -20 $O/det_$n.txt; exit 1; }
-  grep -E "full path|extract:|^diag:" $O/det_$n.txt
+  grep -E "full path|extract:" $O/det_$n.txt
 done
 echo DONE

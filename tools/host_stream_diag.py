@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Host-frame streaming diagnostics on the GPU box: pinned H2D bandwidth by copy size (torch
 pinned tensors, CUDA events), then vo_process_frames_host vs vo_process_frames_device on the same
-sequence (frames/s, rows equal).  Environment knobs (VO_FIRST, ...) apply as usual."""
+sequence (frames/s, rows equal).  Environment knobs apply as usual."""
 import json
 import os
 import sys
