@@ -16,6 +16,8 @@ VO_ERR_IO = -6
 VO_ERR_INTERNAL = -7
 VO_RNG_SPLITMIX = 0
 VO_RNG_MT19937 = 1
+VO_MATCH_RATIO = 0
+VO_MATCH_MUTUAL = 1
 VO_ERR_DEGENERATE_E = -10
 STATUS = {0: "OK", 1: "FIRST", 2: "MISSING", 3: "FEW_MATCHES", 4: "FEW_INLIERS", 5: "DEGENERATE",
           6: "OVERFLOW", 7: "STALLED", 8: "INCONSISTENT"}
@@ -27,7 +29,7 @@ EXPORTS = [
     "vo_trajectory_state", "vo_ring_slots", "vo_rechain", "vo_process_frame",
     "vo_process_frames_device", "vo_process_frames_host", "vo_extract_frames_device", "vo_host_alloc", "vo_host_free", "vo_imread_gray", "vo_device_alloc", "vo_device_free", "vo_device_upload", "vo_device_error_count", "vo_reference_samples", "vo_reset",
     "vo_last_kernel_times", "vo_last_kernel_stats", "vo_enable_kernel_timing", "vo_kernel_form",
-    "vo_unpack_descriptor",
+    "vo_unpack_descriptor", "vo_set_match_mode", "vo_match_mode",
 ]
 
 
@@ -73,6 +75,8 @@ def load():
     L.vo_set_ground_truth.argtypes = [P, P, I]
     L.vo_set_sequence_starts.argtypes = [P, P, I]
     L.vo_set_frame_origin.argtypes = [P, I]
+    L.vo_set_match_mode.argtypes = [P, I]
+    L.vo_match_mode.argtypes = [P]
     L.vo_trajectory_state.argtypes = [P, P]
     L.vo_ring_slots.argtypes = [P]
     L.vo_rechain.argtypes = [P, P, I, I, P]

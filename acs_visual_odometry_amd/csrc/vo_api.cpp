@@ -1008,7 +1008,9 @@ int vo_create(const vo_config* cfg, vo_ctx** out)
                             (size_t)d.max_hyp * WB, (size_t)N * WB, (size_t)d.max_hyp * d.mask_words * WB,
                             (size_t)N * 4 * WB, (size_t)WB, VO_PTS32_PER(N) * WB};
     std::memcpy(c->set_off, per, sizeof(per));
-    rc |= dalloc_rec(c, "match_j", &d.match_j, 2 * per[0]);
+    // each set's match_j is followed by its match_i (VO_MATCH_MUTUAL's backward pass, vo_match_i)
+    c->set_off[0] = 2 * per[0];
+    rc |= dalloc_rec(c, "match_j", &d.match_j, 4 * per[0]);
     rc |= dalloc_rec(c, "match_pairs", &d.match_pairs, 2 * per[1]);
     rc |= dalloc_rec(c, "pts", &d.pts, 2 * per[2]);
     rc |= dalloc_rec(c, "pts32", &d.pts32, 2 * per[9]);
@@ -1187,6 +1189,21 @@ int vo_set_frame_origin(vo_ctx* c, int origin)
     SYNC_ALL(c);
     c->d.origin = origin;
     return VO_OK;
+}
+
+// The mode travels to the kernels in VoDev by value: no device state to update, nothing to wait for
+// (every API call ends synchronised).  vo_reset leaves it alone.
+int vo_set_match_mode(vo_ctx* c, int mode)
+{
+    if (!c || (mode != VO_MATCH_RATIO && mode != VO_MATCH_MUTUAL)) return VO_ERR_ARG;
+    c->d.match_mode = mode;
+    return VO_OK;
+}
+
+int vo_match_mode(vo_ctx* c)
+{
+    if (!c) return VO_ERR_ARG;
+    return c->d.match_mode;
 }
 
 int vo_ring_slots(vo_ctx* c)

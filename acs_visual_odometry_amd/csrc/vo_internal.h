@@ -27,6 +27,8 @@
 //   desc        u64 8N  x SLOTS    packed 512-test descriptors
 //   pre         u32 N   x SLOTS    tests 0..31 (the matcher's 32-bit prefix)
 //   match_j     i32 N        x B   best cur index per prev query, -1 if rejected
+//   match_i     i32 N        x B   VO_MATCH_MUTUAL: best prev index per cur keypoint (no ratio test); the second
+//                                  half of each buffer set's match_j allocation
 //   match_pairs int2 N       x B   (prev, cur) matches, ascending prev index
 //   pts         f64 4N       x B   matched (x1,y1,x2,y2)
 //   pts32       f32 4N       x B   the same in f32, word-swizzled (vo_pts32_index): the Sampson certificate's input
@@ -283,7 +285,7 @@ struct VoDev {
     int2* kps;            // x SLOTS (N each)
     uint64_t* desc;       // x SLOTS (8N each)
     uint32_t* pre;        // x SLOTS (N each)
-    int32_t* match_j;     // x B
+    int32_t* match_j;     // x B, followed by match_i x B (vo_match_i)
     int2* match_pairs;    // x B
     double* pts;          // x B
     float* pts32;         // x B: the same points in f32, per 64-match word [component][j / 4][r][j % 4]
@@ -293,6 +295,10 @@ struct VoDev {
     int32_t* inl;         // x B
     uint64_t* inlmask;    // x B: per hypothesis the Sampson inlier bits of the scored matches
     int mask_words;       // (N + 63) / 64
+    int match_mode;       // VO_MATCH_RATIO / VO_MATCH_MUTUAL (vo_set_match_mode; kept across vo_reset).  It sits in
+                          // what was padding and match_i hangs off match_j (vo_match_i), so the struct -- the
+                          // kernels' first argument -- keeps its size and every other field its offset: the
+                          // default mode's kernels compile to the code they had before the mode existed
     float* model_p;       // x B
     VoWork* work;         // x B
     const uint16_t* maxit_tab;
@@ -330,6 +336,11 @@ __host__ __device__ inline size_t vo_pts32_index(int i, int c)
 {
     const int w = i >> 6, j = (i >> 3) & 7, r = i & 7;
     return (size_t)w * 256 + (size_t)c * 64 + (size_t)(j >> 2) * 32 + (size_t)r * 4 + (size_t)(j & 3);
+}
+// VO_MATCH_MUTUAL's backward pass of window record wf: the N x WB block behind the buffer set's match_j
+__host__ __device__ inline int32_t* vo_match_i(const VoDev& d, int wf)
+{
+    return d.match_j + ((size_t)d.WB + (size_t)wf) * (size_t)d.N;
 }
 // pts32 entries per frame record: whole words
 #define VO_PTS32_PER(N) ((size_t)(((N) + 63) / 64) * 256)

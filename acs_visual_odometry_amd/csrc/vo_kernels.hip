@@ -2636,6 +2636,9 @@ __device__ __forceinline__ bool match_header(const VoDev& d, int stage, const Vo
 // The frame's last workgroup (its first 256 threads): ordered compaction of the accepted queries into
 // (prev, cur) pairs and f64 points, thread t owning queries [t*per, (t+1)*per); M, scored and
 // the < 8 matches status (VisualOdometry.cpp:108-123).
+// MUTUAL (VO_MATCH_MUTUAL, k_match_mutual): query i keeps its accepted candidate j only
+// if the backward pass chose it too, match_i[j] == i; the default instantiation has none of it.
+template <bool MUTUAL = false>
 __device__ void match_compact(const VoDev& d, int wf, const MatchFrame& m, int* s_wsum)
 {
     // rounds of 256 queries (thread t: query 256 u + t), in order: a match's position is the
@@ -2658,6 +2661,15 @@ __device__ void match_compact(const VoDev& d, int wf, const MatchFrame& m, int* 
         for (int u = 0; u < RC; ++u) {
             const int i = (r0 + u) * 256 + tid;
             js[u] = act && i < n1 ? ld_sc1(m.match_j + i) : -1;
+        }
+        if constexpr (MUTUAL) {
+            const int32_t* match_i = vo_match_i(d, wf);
+            int is[RC];
+#pragma unroll
+            for (int u = 0; u < RC; ++u) is[u] = js[u] >= 0 ? ld_sc1(match_i + js[u]) : -1;
+#pragma unroll
+            for (int u = 0; u < RC; ++u)
+                if (is[u] != (r0 + u) * 256 + tid) js[u] = -1;
         }
         int2 ka[RC], kb[RC];
 #pragma unroll
@@ -2889,6 +2901,191 @@ __global__ void __launch_bounds__(256) k_match512(VoDev d, int stage)
     }
     if (!arrive_last(&m.w->ctr[0], gridDim.x, &s_last)) return;
     match_compact(d, wf, m, s_wsum);
+}
+
+// ---------------------------------------------------------------------------
+// Mutual-nearest-neighbour matching (vo_set_match_mode VO_MATCH_MUTUAL): the pair (i, j) of the
+// ratio-test matcher above is kept only if i is also j's best match in the other direction,
+// back[j] = argmin_i (dist(i, j) << 16 | i) over the prev frame (first-index minimum, no ratio test).
+// One launch does both directions: grid (2 x blocks, B), the first half of a frame's workgroups are
+// the forward matcher above (queries prev, candidates cur, top-2 + ratio -> match_j), the second
+// half the backward pass with the roles swapped (queries cur, candidates prev, top-1 -> match_i).
+// Both kinds arrive at the frame's counter; the last one compacts with the extra test
+// match_i[match_j[i]] == i (match_compact<true>).  match_i is stored and loaded sc1 like match_j.
+// VO_MATCH_RATIO launches none of this.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t min3_u32(uint32_t a, uint32_t b, uint32_t c)
+{
+    uint32_t r;
+    asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ int top1_index(uint32_t m1) { return m1 == 0xFFFFFFFFu ? -1 : (int)(m1 & 0xFFFF); }
+
+// One direction of the 32-test matcher for workgroup bx of its side: k_match's body with the query
+// and candidate slots as arguments.  TOP1: the backward pass keeps the minimum key only (one
+// v_min3_u32 per two candidates, the same even / odd chains) and stores its index.
+template <int QPL, int NW, bool TOP1>
+__device__ __forceinline__ void match32_side(const VoDev& d, int bx, int qslot, int cslot, int nq, int nc, int32_t* out,
+                                             uint4* s_cand4, uint2 (*s_top)[QPL][64])
+{
+    constexpr int NT = 64 * NW;
+    uint32_t* s_cand = reinterpret_cast<uint32_t*>(s_cand4);
+    const int N = d.N;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t* cand = d.pre + (size_t)cslot * N;
+    for (int j0 = threadIdx.x; j0 < nc; j0 += 4 * NT) {
+        uint32_t v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = j0 + u * NT < nc ? cand[j0 + u * NT] : 0u;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (j0 + u * NT < nc) s_cand[j0 + u * NT] = v[u];
+    }
+    uint32_t qv[QPL];
+#pragma unroll
+    for (int u = 0; u < QPL; ++u) {
+        const int q = bx * (64 * QPL) + 64 * u + lane;
+        qv[u] = q < nq ? d.pre[(size_t)qslot * N + q] : 0u;
+    }
+    const int qs = ((nc + 4 * NW - 1) / (4 * NW)) * 4;
+    const int j0 = min(wave * qs, nc), j1 = min(j0 + qs, nc);
+    uint32_t a1[QPL], a2[QPL], b1[QPL], b2[QPL];
+#pragma unroll
+    for (int u = 0; u < QPL; ++u) a1[u] = a2[u] = b1[u] = b2[u] = 0xFFFFFFFFu;
+    __syncthreads();
+    int j = j0;
+    for (; j + 4 <= j1; j += 4) {
+        const uint4 c = s_cand4[j >> 2];
+#pragma unroll
+        for (int u = 0; u < QPL; ++u) {
+            const uint32_t k0 = ((uint32_t)__popc(qv[u] ^ c.x) << 16) | (uint32_t)j;
+            const uint32_t k1 = ((uint32_t)__popc(qv[u] ^ c.y) << 16) | (uint32_t)(j + 1);
+            const uint32_t k2 = ((uint32_t)__popc(qv[u] ^ c.z) << 16) | (uint32_t)(j + 2);
+            const uint32_t k3 = ((uint32_t)__popc(qv[u] ^ c.w) << 16) | (uint32_t)(j + 3);
+            if constexpr (TOP1) {
+                a1[u] = min3_u32(a1[u], k0, k1);
+                b1[u] = min3_u32(b1[u], k2, k3);
+            } else {
+                top2_insert2(k0, k1, a1[u], a2[u]);
+                top2_insert2(k2, k3, b1[u], b2[u]);
+            }
+        }
+    }
+    for (; j < j1; ++j) {
+        const uint32_t cj = s_cand[j];
+#pragma unroll
+        for (int u = 0; u < QPL; ++u) {
+            const uint32_t k = ((uint32_t)__popc(qv[u] ^ cj) << 16) | (uint32_t)j;
+            if constexpr (TOP1) a1[u] = min(a1[u], k);
+            else top2_insert(k, a1[u], a2[u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < QPL; ++u) {
+        if constexpr (TOP1) a1[u] = min(a1[u], b1[u]);
+        else top2_merge(a1[u], a2[u], b1[u], b2[u]);
+        if (wave > 0) s_top[wave - 1][u][lane] = make_uint2(a1[u], a2[u]);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int u = 0; u < QPL; ++u) {
+#pragma unroll
+            for (int w = 0; w < NW - 1; ++w) {
+                const uint2 o = s_top[w][u][lane];
+                if constexpr (TOP1) a1[u] = min(a1[u], o.x);
+                else top2_merge(a1[u], a2[u], o.x, o.y);
+            }
+            const int q = bx * (64 * QPL) + 64 * u + lane;
+            if (q < nq) st_sc1(out + q, TOP1 ? top1_index(a1[u]) : ratio_accept(a1[u], a2[u], d.ratio));
+        }
+    }
+}
+
+// One direction of the 512-test matcher (k_match512's body, slots as arguments); TOP1 as above.
+// The candidate side's descriptors stream through the same LDS tile in either direction.
+template <bool TOP1>
+__device__ __forceinline__ void match512_side(const VoDev& d, int bx, int qslot, int cslot, int nq, int nc, int32_t* out,
+                                              uint4* s_tile)
+{
+    const int N = d.N;
+    const int q = bx * MT512_QPB + threadIdx.x;
+    const bool wave_live = __builtin_amdgcn_readfirstlane(bx * MT512_QPB + (threadIdx.x & ~63)) < nq;
+    uint32_t qw[16];
+    {
+        const uint4* qd = reinterpret_cast<const uint4*>(d.desc + ((size_t)qslot * N + (q < nq ? q : 0)) * 8);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const uint4 v = qd[g];
+            qw[4 * g] = v.x; qw[4 * g + 1] = v.y; qw[4 * g + 2] = v.z; qw[4 * g + 3] = v.w;
+        }
+    }
+    uint32_t m1 = 0xFFFFFFFFu, m2 = 0xFFFFFFFFu;
+    const uint4* cd = reinterpret_cast<const uint4*>(d.desc + (size_t)cslot * N * 8);
+    for (int t0 = 0; t0 < nc; t0 += MT512_TILE) {
+        const int nt = min(MT512_TILE, nc - t0);
+        __syncthreads();                                  // the previous tile is consumed
+        for (int c = threadIdx.x; c < nt * 4; c += 256) s_tile[c] = cd[(size_t)t0 * 4 + c];
+        __syncthreads();
+        if (wave_live) {
+            int j = 0;
+            for (; j + 1 < nt; j += 2) {
+                const uint32_t da = dist512(qw, s_tile + 4 * j), db = dist512(qw, s_tile + 4 * j + 4);
+                const uint32_t ka = (da << 16) | (uint32_t)(t0 + j), kb = (db << 16) | (uint32_t)(t0 + j + 1);
+                if constexpr (TOP1) {
+                    m1 = min3_u32(m1, ka, kb);
+                } else {
+                    top2_insert(ka, m1, m2);
+                    top2_insert(kb, m1, m2);
+                }
+            }
+            if (j < nt) {
+                const uint32_t k = (dist512(qw, s_tile + 4 * j) << 16) | (uint32_t)(t0 + j);
+                if constexpr (TOP1) m1 = min(m1, k);
+                else top2_insert(k, m1, m2);
+            }
+        }
+    }
+    if (q < nq) st_sc1(out + q, TOP1 ? top1_index(m1) : ratio_accept(m1, m2, d.ratio));
+}
+
+// The kernel, one template for both widths (every instantiation is requested by launch_match_mutual
+// at the end of this file, so the code object lays them out after the default mode's kernels, which
+// keep their places).  BITS 32: the k_match forms (QPL queries per lane, NW waves); BITS 512: the
+// k_match512 form (dynamic LDS tile, QPL and NW unused).
+template <int BITS, int QPL = 1, int NW = 4>
+__global__ void __launch_bounds__(64 * NW) k_match_mutual(VoDev d, int stage)
+{
+    const int wf = blockIdx.y;
+    const VoPlan P = match_window(d, stage);
+    if (wf >= vwin_records(P)) return;
+    MatchFrame m;
+    if (!match_header(d, stage, P, wf, m)) return;       // workgroup 0 (a forward one) writes the header
+    __shared__ unsigned s_last;
+    __shared__ int s_wsum[32];                       // match_compact: 8 rounds x 4 waves
+    const int side = gridDim.x >> 1;                 // workgroups per direction
+    const bool bwd = blockIdx.x >= side;
+    const int bx = bwd ? blockIdx.x - side : blockIdx.x;
+    int32_t* match_i = vo_match_i(d, wf);
+    if constexpr (BITS == 32) {
+        __shared__ uint4 s_cand4[1024];              // 4096 prefixes
+        __shared__ uint2 s_top[NW - 1][QPL][64];
+        if (!bwd && bx * (64 * QPL) < m.n1)
+            match32_side<QPL, NW, false>(d, bx, m.prev, m.cur, m.n1, m.n2, m.match_j, s_cand4, s_top);
+        if (bwd && bx * (64 * QPL) < m.n2)
+            match32_side<QPL, NW, true>(d, bx, m.cur, m.prev, m.n2, m.n1, match_i, s_cand4, s_top);
+        if (blockIdx.x == 0) VO_STAMP(d, 1993, 1);
+    } else {
+        static_assert(NW == 4, "the 512-test form runs 256 threads");
+        extern __shared__ uint4 s_tile[];            // MT512_TILE x 64 B
+        if (!bwd && bx * MT512_QPB < m.n1)
+            match512_side<false>(d, bx, m.prev, m.cur, m.n1, m.n2, m.match_j, s_tile);
+        if (bwd && bx * MT512_QPB < m.n2)
+            match512_side<true>(d, bx, m.cur, m.prev, m.n2, m.n1, match_i, s_tile);
+    }
+    if (!arrive_last(&m.w->ctr[0], gridDim.x, &s_last)) return;
+    match_compact<true>(d, wf, m, s_wsum);
 }
 
 
@@ -5077,7 +5274,9 @@ const char* kernel_form(const VoDev& d, int k)
     case 0: return "k_stencil";
     case 1: return d.sel1 ? "k_select" : "k_select_count,k_select_emit";
     case 2: return "k_describe";
-    case 3: return d.match_bits == 32 ? "k_match" : "k_match512";
+    case 3:
+        if (d.match_mode == VO_MATCH_MUTUAL) return "k_match_mutual";   // both widths: one template
+        return d.match_bits == 32 ? "k_match" : "k_match512";
     case 4: return "k_ransac_hyp";
     case 5: return "k_refit";
     case 6: return "k_triangulate";
@@ -5086,8 +5285,10 @@ const char* kernel_form(const VoDev& d, int k)
     }
     return "";
 }
+static void launch_match_mutual(const VoDev& d, int stage, hipStream_t s);   // at the end of the file
 void launch_match(const VoDev& d, int stage, hipStream_t s)
 {
+    if (d.match_mode == VO_MATCH_MUTUAL) return launch_match_mutual(d, stage, s);
     if (d.match_bits == 32) {
         // single-frame calls: one query per lane (4x the workgroups, a quarter of the walk each)
         if (d.single)
@@ -5197,6 +5398,28 @@ void launch_selftest_arith(const float* fa, const float* fb, float* fo, const do
                            double* dout, int n, hipStream_t s)
 {
     hipLaunchKernelGGL(k_selftest_arith, dim3((n + 255) / 256), dim3(256), 0, s, fa, fb, fo, da, db, dout, n);
+}
+
+// VO_MATCH_MUTUAL: both directions in one launch, twice launch_match's workgroups per frame.  Kept
+// last: k_match_mutual's instantiations follow every other kernel in the code object.
+static void launch_match_mutual(const VoDev& d, int stage, hipStream_t s)
+{
+    const int gy = stage ? 1 : d.gridw;
+    if (d.match_bits == 32) {
+        if (d.single)
+            hipLaunchKernelGGL((k_match_mutual<32, 1, MT_SINGLE_WAVES>), dim3(2 * ((d.N + 63) / 64), gy),
+                               dim3(64 * MT_SINGLE_WAVES), 0, s, d, stage);
+        else
+            hipLaunchKernelGGL((k_match_mutual<32, MT_QPL>), dim3(2 * match_blocks(d.N, 32), gy), dim3(256), 0, s, d, stage);
+    } else {
+        // 64 KB of dynamic LDS plus the static hand-off words, as k_match512
+        static const bool lds_ok = hipFuncSetAttribute((const void*)k_match_mutual<512>,
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                       MT512_TILE * 64) == hipSuccess;
+        (void)lds_ok;
+        hipLaunchKernelGGL((k_match_mutual<512>), dim3(2 * match_blocks(d.N, 512), gy), dim3(256),
+                           (size_t)MT512_TILE * 64, s, d, stage);
+    }
 }
 
 }  // namespace vo

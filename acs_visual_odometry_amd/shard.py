@@ -261,7 +261,9 @@ def run_local(engines: Sequence, nframes: int, halo: int = DEFAULT_HALO) -> List
 class ContextEngine:
     """A shard's engine over a Context: the sequence's frames and GT rows.  frames: host
     (F x H x W u8, uploaded per run) or a DeviceFrames batch of the whole sequence, or of the
-    frames from `base` on (resident in HBM; a run uses a view of it)."""
+    frames from `base` on (resident in HBM; a run uses a view of it).  The context's match mode
+    (Context(match_mode=...) / set_match_mode) is kept across the resets of run(), so every shard
+    built with the same keyword matches as the unsplit run does."""
 
     def __init__(self, ctx, frames, gt: Optional[np.ndarray] = None, base: int = 0):
         self.ctx, self.frames, self.gt, self.base = ctx, frames, gt, base

@@ -27,11 +27,18 @@ class Context:
 
     def __init__(self, width: int, height: int, **cfg):
         self.lib = load()
+        match_mode = cfg.pop("match_mode", _lib.VO_MATCH_RATIO)   # not a vo_config field: vo_set_match_mode
         self.cfg = _lib.default_config(width, height, **cfg)
         h = C.c_void_p()
         check(self.lib.vo_create(C.byref(self.cfg), C.byref(h)), "vo_create")
         self.h = h
         self.W, self.H, self.N = width, height, self.cfg.max_kpts
+        if match_mode != _lib.VO_MATCH_RATIO:
+            try:
+                self.set_match_mode(match_mode)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None):
@@ -139,6 +146,14 @@ class Context:
         """The stream's first frame is frame `origin` of its sequence (a sequence shard,
         vo_set_frame_origin): RANSAC draws the hypotheses of the unsplit run."""
         check(self.lib.vo_set_frame_origin(self.h, int(origin)), "vo_set_frame_origin")
+
+    def set_match_mode(self, mode: int):
+        """VO_MATCH_RATIO (0, default) or VO_MATCH_MUTUAL (1, cross-check: a pair is kept only if each
+        keypoint is the other's nearest); vo_set_match_mode.  Kept across reset()."""
+        check(self.lib.vo_set_match_mode(self.h, int(mode)), "vo_set_match_mode")
+
+    def match_mode(self) -> int:
+        return check(self.lib.vo_match_mode(self.h), "vo_match_mode")
 
     def trajectory_state(self) -> np.ndarray:
         """T_curr after the last committed frame (4x4)."""
@@ -329,14 +344,17 @@ class VisualOdometry:
     ``kernel_filename`` is accepted for signature compatibility (the reference loads an
     OpenCL binary, main_pipeline.cpp:32); the HIP code objects are embedded in
     libvo_mi355x.so.  ``num_threads`` keeps its one semantic effect on the results:
-    the RANSAC chunk count (ransac.cpp:152-157).
+    the RANSAC chunk count (ransac.cpp:152-157).  ``cross_check=True`` keeps only mutual nearest
+    neighbours among the ratio-test matches (VO_MATCH_MUTUAL; the reference has no such option).
     """
 
     def __init__(self, kernel_filename: str = "", num_threads: int = 8, width: int = 1241, height: int = 376,
-                 **cfg):
+                 cross_check: bool = False, **cfg):
         self.kernel_filename = kernel_filename
         self.number_of_threads = int(num_threads)
         cfg.setdefault("ransac_chunk_threads", max(self.number_of_threads, 1))
+        if cross_check:
+            cfg["match_mode"] = _lib.VO_MATCH_MUTUAL
         self._cfg = cfg
         self.ctx = Context(width, height, **cfg)
 

@@ -242,6 +242,15 @@ public:
         return {desc, out};
     }
 
+    // Cross-check matching (not in the reference; off by default): match_descriptors and the
+    // trajectory calls keep a ratio-test match (i, j) only if i is also j's nearest keypoint of the
+    // previous frame (vo_set_match_mode VO_MATCH_MUTUAL).
+    void set_cross_check(bool on)
+    {
+        check(vo_set_match_mode(ctx_, on ? VO_MATCH_MUTUAL : VO_MATCH_RATIO), "vo_set_match_mode");
+    }
+    bool cross_check() const { return vo_match_mode(ctx_) == VO_MATCH_MUTUAL; }
+
     // match_descriptors (VisualOdometry.h:27-29)
     std::vector<std::pair<int, int>> match_descriptors(const std::vector<std::vector<uint8_t>>& desc1,
                                                        const std::vector<std::vector<uint8_t>>& desc2)

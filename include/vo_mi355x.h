@@ -182,6 +182,18 @@ int  vo_set_sequence_starts(vo_ctx* ctx, const int32_t* starts, int n);
  * sampler of the stream's first sequence counts frames from origin, so every frame draws the
  * hypotheses it draws in the unsplit run.  Kept across vo_reset; 0 = an ordinary stream. */
 int  vo_set_frame_origin(vo_ctx* ctx, int origin);
+
+/* Which matches the matcher keeps.  VO_MATCH_RATIO (default, the reference): prev keypoint i is
+ * paired with its nearest cur keypoint j if Lowe's ratio test accepts it.  VO_MATCH_MUTUAL
+ * (cross-check): such a pair is kept only if i is also j's nearest prev keypoint -- the first-index
+ * minimum of (distance << 16 | i) over the prev frame, at the same descriptor width (match_bits), with
+ * no ratio test on that side.  The result is a subsequence of VO_MATCH_RATIO's pairs; everything after
+ * the matcher sees the smaller set.  Applies to vo_match and every trajectory call from the next call
+ * on; kept across vo_reset.  Returns VO_ERR_ARG for a null context or another value (the mode stays). */
+#define VO_MATCH_RATIO  0
+#define VO_MATCH_MUTUAL 1
+int  vo_set_match_mode(vo_ctx* ctx, int mode);
+int  vo_match_mode(vo_ctx* ctx);            /* the current mode, or VO_ERR_ARG for a null context */
 /* Frames whose keypoints, descriptors and trajectory records stay resident on the device (the
  * ring: 4096 by default, VO_RING_SLOTS): vo_rechain reaches back this far, so a shard may hold at
  * most this many frames.  Returns the count (> 0) or an error code. */
